@@ -32,12 +32,21 @@ and configs[3] (Panda, approximate-solution mode, 65 536 unreachable targets per
 answers -- every problem returns its best individual), one call per step; the N = 1 line of the default
 config carries both as legs (`config3`, `config4`).
 
-After the timed headline region rank 0 (N = 1) appends further legs to the same JSON line, each timed
-on its own: `sustained` (512 steps in pools of 64 on 4 streams: the throughput regime), `single_batch`
-(one isolated 4096-target call at a time, median of 24), `config3` / `config4`, `other_robots` (arithmetic = exact on a
-nine-variable chain, a two-tip tree and a chain on a floating base, each checked against the oracle), the other flavour (`fast`, with
-the same legs inside), `plain_ieee` (the verification library: no fused operation anywhere),
-`value_incl_h2d_d2h` (host-pointer entry point) and `cpu_baseline` (the oracle on the host cores).
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last
+timed step when `--dump-outputs DIR` is given, and the JSON line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, `config`, ...).  With `--full`, after the timed headline region rank 0 (N = 1) appends
+further legs to the same JSON line, each timed on its own: `sustained` (512 steps in pools of 64 on 4 streams: the
+throughput regime), `single_batch` (one isolated 4096-target call at a time, median of 24), `config3` / `config4`,
+`other_robots` (arithmetic = exact on a nine-variable chain, a two-tip tree and a chain on a floating base, each
+checked against the oracle), the other flavour (`fast`, with the same legs inside), `plain_ieee` (the verification
+library: no fused operation anywhere), `value_incl_h2d_d2h` (host-pointer entry point) and `cpu_baseline` (the
+oracle on the host cores); the headline's `roofline` and its `parity` against the oracle are `--full` figures too.
+The `--no-legs` / `--no-strict` / `--no-pcie` / `--cpu-sample 0` switches pick parts of a `--full` run.
+
+`--dump-outputs DIR` (rank 0): the arrays a caller of the timed path receives for the LAST timed step --
+`solution` [B, dof], `status` [B], `final_cost` [B], `stats` [B, 4] (cost_evals, generations, wipeouts,
+pool_erasures) -- as DIR/<name>.npy in float64; above 60 MB in all, a fixed, seeded sample of the problems (their
+indices in DIR/sample_index.npy).  The inputs are seeded: the same arguments give the same inputs on every run.
 
 Prints ONE JSON line on rank 0 (fields documented in DESIGN.md "Measurement").
 """
@@ -55,8 +64,8 @@ if ROOT not in sys.path:
 
 # Independent calls are overlapped on separate HIP streams.  The HIP runtime multiplexes streams
 # onto GPU_MAX_HW_QUEUES hardware queues (default 4; measured: N queues -> N/2 kernels in flight),
-# so the limit has to be raised before the runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "256")
+# so the limit has to be raised before the runtime initialises (32: well above the streams this script opens).
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 import numpy as np  # noqa: E402
 
@@ -124,17 +133,29 @@ def parse():
                     help="the flavour of the HEADLINE region.  exact (default): the product library's literal kernels "
                          "(option arithmetic = exact), whose joint vectors are identical to the oracle's; fast: the "
                          "Denavit-Hartenberg / frame-probe kernels.  The other flavour is timed as a leg of the line")
-    ap.add_argument("--no-strict", action="store_true", help="skip the other flavour's leg and the plain-IEEE library's timing")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-pointer (PCIe-inclusive) timing")
-    ap.add_argument("--no-legs", action="store_true", help="skip the sustained / single-batch / config 3, 4 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: legs, the other flavour, the plain-IEEE library, parity "
+                         "against the oracle, host-pointer path, native front end, CPU baseline, roofline (a plain "
+                         "run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (solution, status, final_cost, stats) to DIR/<name>.npy "
+                         "in float64 (at most 64 MB: a fixed, seeded sample of the problems above that)")
+    ap.add_argument("--no-strict", action="store_true", help="(--full) skip the other flavour's leg and the plain-IEEE library's timing")
+    ap.add_argument("--no-pcie", action="store_true", help="(--full) skip the host-pointer (PCIe-inclusive) timing")
+    ap.add_argument("--no-legs", action="store_true", help="(--full) skip the sustained / single-batch / config 3, 4 legs")
     ap.add_argument("--launch-check", action="store_true",
-                    help="only start the ranks, form the process group (gloo without GPUs), all-reduce a "
+                    help="only start the ranks, form the process group (gloo with fewer GPUs than ranks), all-reduce a "
                          "one per rank and report the world size: the launch path without the solver")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 8 if args.config != 2 else 512
     if args.warmup is None:
         args.warmup = 2 if args.config != 2 else 64
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the headline region alone
+        args.no_strict = args.no_pcie = args.no_legs = True
+        args.cpu_sample = 0
     if args.config in BIG_CONFIGS:
         args.robot = BIG_CONFIGS[args.config]["robot"]
     return args
@@ -214,6 +235,31 @@ class RooflineInputs:
                 "inputs_stale": self.stale(r, kernel_name)}
 
 
+MAX_DUMP_BYTES = 60 * 10**6  # (the .npy headers and a sample's indices stay under 64 MB too)
+DUMP_SAMPLE_SEED = 0x44554D50
+
+
+def dump_outputs(path, solution, status, final_cost, stats):
+    """--dump-outputs: what a caller of the timed path receives for one step, as float64 .npy files.  `stats` is the
+    [B, 3] int64 view of pikamd_stats (int64 cost_evals; int32 generations, wipeouts, pool_erasures, reserved).
+    Above MAX_DUMP_BYTES the same fixed, seeded sample of the problems is written for every array."""
+    raw = stats.reshape(len(stats), 3)
+    i32 = raw.view(np.int32).reshape(len(stats), 6)
+    arrays = {"solution": solution, "status": status, "final_cost": final_cost,
+              "stats": np.stack([raw[:, 0], i32[:, 2], i32[:, 3], i32[:, 4]], axis=1)}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(status)
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > MAX_DUMP_BYTES:
+        keep = MAX_DUMP_BYTES // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def self_launch(args) -> int:
     """`bench.py --gpus N` started without a launcher: start the N ranks (one per GPU) ourselves."""
     import socket
@@ -238,7 +284,8 @@ def launch_check(args, world, rank, local_rank):
     """The launch path alone: N ranks, one process group, one all-reduce."""
     import torch
     import torch.distributed as dist
-    cuda = torch.cuda.is_available()
+    # (every rank decides alike: RCCL when each rank has a device of its own, else gloo on the host)
+    cuda = torch.cuda.is_available() and torch.cuda.device_count() >= world
     if cuda:
         torch.cuda.set_device(local_rank)
     if "MASTER_ADDR" not in os.environ:
@@ -458,6 +505,10 @@ def main():
     converged_total, evals_total = float(totals[0]), float(totals[1])
     mean_gens = float(totals[2]) / world
     call_ms = [a.elapsed_time(b) for a, b in ev]
+    if rank == 0 and args.dump_outputs:
+        last = W + K - 1
+        dump_outputs(args.dump_outputs, sols[last].cpu().numpy(), status[last].cpu().numpy(),
+                     costs[last].cpu().numpy(), stats_[last].cpu().numpy())
 
     result_line = None
     if rank == 0:
@@ -534,7 +585,9 @@ def main():
                                     "fast: Denavit-Hartenberg frames + frame-based gradient probes; agrees with the "
                                     "oracle statistically (success rate, costs), not joint vector by joint vector"),
             },
-            "roofline": {
+        }
+        if args.full:  # (the staleness check of the profiled inputs preprocesses the device source)
+            out["roofline"] = {
                 "bound": "fp64_valu",
                 "kernel": kname,
                 "achieved": exec_tflops,
@@ -580,8 +633,7 @@ def main():
                                 "calibrated": (issue_roof(rin.get("valu_classes_per_problem"), per_launch / avg_launch_s)
                                                if rin.get("valu_classes_per_problem") else None)}
                                if valu_pp else None),
-            },
-        }
+            }
         out["n_ranks"] = dist.get_world_size() if use_dist else 1
         out["launch"] = ("self (bench.py started its ranks)" if os.environ.get("PIK_BENCH_SELF_LAUNCHED") == "1"
                          else "external launcher" if "WORLD_SIZE" in os.environ else "single process")

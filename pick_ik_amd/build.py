@@ -316,6 +316,17 @@ def write_ledger(path: str = LEDGER):
     return path
 
 
+def build_jobs() -> int:
+    """parallel compilations: MAX_JOBS when set, else the CPUs this process may run on (os.cpu_count() counts the
+    whole host, which on a shared host is more than the process is given)"""
+    if os.environ.get("MAX_JOBS", "").isdigit() and int(os.environ["MAX_JOBS"]) > 0:
+        return int(os.environ["MAX_JOBS"])
+    try:
+        return max(1, len(os.sched_getaffinity(0)))
+    except AttributeError:
+        return max(1, os.cpu_count() or 1)
+
+
 def build_library(force: bool = False, verbose: bool = False, strict_too: bool = True) -> str:
     """Builds the product library and the strict-arithmetic verification library.
 
@@ -341,7 +352,7 @@ def build_library(force: bool = False, verbose: bool = False, strict_too: bool =
                     return -int(fl.split("=")[1])
             return -100
         jobs.sort(key=length_of)
-        with cf.ThreadPoolExecutor(max_workers=max(1, os.cpu_count() or 1)) as ex:
+        with cf.ThreadPoolExecutor(max_workers=build_jobs()) as ex:
             for f in [ex.submit(_compile, *o, strict, verbose) for o, strict in jobs]:
                 f.result()
     for lib, objs in relink:

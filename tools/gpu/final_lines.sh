@@ -3,7 +3,7 @@
 set -u
 TAG=${1:-r06final}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-line() { local name=$1; shift; python bench.py "$@" 2> $OUT/$name.err | grep "^{" | tail -1 > $OUT/$name.json; python - $OUT/$name.json <<'PY'
+line() { local name=$1; shift; python bench.py --full "$@" 2> $OUT/$name.err | grep "^{" | tail -1 > $OUT/$name.json; python - $OUT/$name.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]; f = d.get("fast", {})
 print(sys.argv[1], d["config"]["arithmetic"], round(d["value"]), round(d["ms_per_step"], 4), "frac", r["frac"] and round(r["frac"], 4),

@@ -3,7 +3,7 @@ set -u
 TAG=${1:-r04x}
 REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --no-legs --no-pcie --cpu-sample 0 > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-legs --no-pcie --cpu-sample 0 > $OUT/bench.log 2>&1
 cd $REPO
 f=$(find $OUT/kt -name "*kernel_trace.csv" | head -1)
 for ns in pik_exact pik_strict; do

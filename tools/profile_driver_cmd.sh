@@ -12,7 +12,7 @@ ARGS=${@:---gpus 1 --steps 20 --warmup 5}
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT; echo "$ARGS" > $OUT/args.txt
-CLEAN="--cpu-sample 0 --no-strict --no-pcie --no-legs"
+CLEAN="--full --cpu-sample 0 --no-strict --no-pcie --no-legs"
 cd /tmp && export TMPDIR=/tmp
 run() { # name, counters...
     local name=$1; shift
@@ -28,7 +28,7 @@ run pmc_write WRITE_SIZE
 cd $REPO
 grep "^{" $OUT/kt_bench.log | tail -1 > $OUT/bench_line.json
 if [ -z "${PIK_PROFILE_SKIP_FULL:-}" ]; then  # (tools/gpu/final_lines.sh takes the full lines of the final library anyway)
-    python bench.py $ARGS --cpu-sample 0 > $OUT/full_bench.log 2>&1
+    python bench.py $ARGS --full --cpu-sample 0 > $OUT/full_bench.log 2>&1
     grep "^{" $OUT/full_bench.log | tail -1 > $OUT/bench_line_full.json
 fi
 python tools/read_prof.py $OUT --json $OUT/summary.json > $OUT/summary.txt 2>&1

@@ -30,7 +30,7 @@ if __name__ == "__main__":
                 env[k] = v
             else:
                 args.append(tok)
-        d = run(args + ["--cpu-sample", "0"], env)
+        d = run(args + ["--full", "--cpu-sample", "0"], env)
         if d:
             r = d["roofline"]
             c = d["config"]
