@@ -28,7 +28,9 @@
  *   in this mode the oracle and a GPU build without FMA contraction must agree BIT FOR BIT; that
  *   is how the kernels' control flow (random streams, mating pool, selection, wipeouts) is
  *   verified despite the chaotic sensitivity of the gradient descent (DESIGN.md "Parity").
- *   Mode 1 differs from mode 0 by <= 1 ulp per call (tests/test_oracle_golden.py).
+ *   Mode 1's sine / cosine are within 2 ulp of the true values for |x| <= 65536 + pi (6e-16 absolute beyond), its
+ *   arctangent within 2 ulp; mode 2's arctangent within 3 ulp (tests/test_gpu_math_accuracy.py and
+ *   tests/test_host_math_cpu.py test_math_accuracy_host_half, which sweep the library's copies of these functions).
  * math mode 2 ("fma"): mode 1's algorithm with fused multiply-adds AT STATED PLACES -- the row
  *   products of the chain (iso_mul), the sums of squares of the two distances, the relative
  *   quaternion, the cost accumulations (pose cost, joint-goal sums), the gradient-step update -- and

@@ -282,7 +282,13 @@ inline void build_dh(ChainHost& c) {
         v_cross(z, zn, w);
         const double sw2 = v_dot(w, w);
         double d = 0.0, aa = 0.0;
-        if (sw2 > 1e-24 && sw2 < 1e-6) {
+        // The window of the general step: above sw2 = 1e-30 (1e-15 rad) taking the axes as parallel would move the
+        // next frame by ~0.5 L angle, more than rounding; below sw2 = 1e-3 (0.032 rad) the DH offsets cancel to
+        // ~1e-16 L / angle, more than rounding too -- above it that is <= 3e-15 L, within the FK bound of
+        // tests/test_gpu_fk_accuracy.py, and chains with such pairs keep the branch-free loop and the kernels for the
+        // common configuration (tests/test_host_math_cpu.py test_nearly_parallel_axes_fast_fk_on_host,
+        // tests/test_gpu_fk_accuracy.py test_ur5_axis_perturbation_sweep).
+        if (sw2 > 1e-30 && sw2 < 1e-3) {
             // Nearly but not exactly parallel axes (e.g. rpy = "1.57079632679" written for pi/2 is
             // 4.9e-12 rad off): the common normal's foot is ~L / sin(angle) away, the DH offsets d
             // of this step and the next cancel to 1e-16 L / angle -- 3e-5 m at 3e-12 rad.  Such a
@@ -306,7 +312,7 @@ inline void build_dh(ChainHost& c) {
             }
             continue;
         }
-        if (sw2 > 1e-24) { // skew or intersecting axes
+        if (sw2 > 1e-30) { // skew or intersecting axes
             const double sw = std::sqrt(sw2);
             for (int i = 0; i < 3; ++i) nrm[i] = w[i] / sw;
             aa = v_dot(delta, nrm);
@@ -325,7 +331,7 @@ inline void build_dh(ChainHost& c) {
             double perp[3];
             for (int i = 0; i < 3; ++i) perp[i] = delta[i] - dz * z[i];
             aa = v_norm(perp);
-            if (aa > 1e-12) {
+            if (aa > 1e-15) { // (below: the same line, within 1e-15 m -- rounding of a metre-sized chain)
                 for (int i = 0; i < 3; ++i) nrm[i] = perp[i] / aa;
             } else { // the same line
                 aa = 0.0;

@@ -408,7 +408,9 @@ PIK_HD double sqrt_pos(double x) {
 // All four cases are written out over statically indexed differences/sums and combined with
 // selects between *computed scalars* (never between array elements, which the compiler would
 // turn into a dynamically indexed -- i.e. scratch/LDS resident -- copy of R); one sqrt and one
-// divide are shared by all cases and a wave never diverges here.
+// divide are shared by all cases and a wave never diverges here.  Within 5e-16 per component of the exact quaternion
+// (up to sign) of a rotation rounded to doubles, near angle pi, trace 0 and ties of the diagonal too (measured
+// 3.5e-16; tests/test_gpu_math_accuracy.py).
 PIK_HD void matrix_to_quat(const double (&R)[9], double (&q)[4]) {
     const double m00 = R[0], m11 = R[4], m22 = R[8];
     const double tr = m00 + m11 + m22;
@@ -685,10 +687,17 @@ PIK_HD void iso_mul_r(double (&R)[9], double (&t)[3], const double (&o)[12]) {
 
 // sin and cos of a joint angle.  Replaces libm's sin/cos (what MoveIt's
 // RevoluteJointModel::computeTransform calls): Cody-Waite reduction by pi/2 with a three-double
-// split and FMAs (exact to < 1 ulp of the reduced argument for |x| < ~1e5 rad, which covers every
+// split and FMAs (accurate far below an ulp of the reduced argument for |x| < ~1e5 rad, which covers every
 // joint range; larger magnitudes are first folded by 2 pi), then the fdlibm minimax kernels on
 // [-pi/4, pi/4].  No table, no stack array, no divergence: ~35 FP64 instructions versus the ~80
 // plus scratch of the generic large-argument routine.
+// Accuracy, asserted by tests/test_gpu_math_accuracy.py (device, all three flavours, bit-identical to the host) and
+// tests/test_host_math_cpu.py test_math_accuracy_host_half:
+//   |x| <= 65536 + pi: <= 2 ulp (the reduction is exact to far below an ulp, the kernels' error of about an ulp is the error;
+//                      measured 1.48 ulp, 0.99 ulp within a few ulp of k pi / 2);
+//   |x| >  65536:      <= 6e-16 absolute (fold_2pi rounds the folded argument, <= 4.5e-16, plus the in-range error;
+//                      measured 2.9e-16) -- not relative: near a zero of sin / cos the relative error is unbounded.
+//   sin(+-0) = +0 (the reduction's x - 0 pi/2 drops the sign of a zero), cos(+-0) = 1; +-inf and NaN give NaN.
 using MT = const PIK_CONSTANT MathTab&;
 
 // The same 38 coefficients as compile-time literals.  Used as VALU multiplicands they are
@@ -892,7 +901,8 @@ PIK_HD double flip_sign(double x, uint32_t hi_mask) {
     return x;
 }
 
-// x - 2 pi rint(x / 2 pi) for |x| > 65536 (10^4 revolutions), x otherwise
+// x - 2 pi rint(x / 2 pi) for |x| > 65536 (10^4 revolutions), x otherwise; <= 4.5e-16 from the exact difference
+// with the same k (two fused steps, each rounding a result of magnitude < 4; tests/test_gpu_math_accuracy.py)
 PIK_HD double fold_2pi(MT m, double x) {
     const bool big = fabs(x) > 65536.0;
     const double k = big ? rint(x * PIK_MV(m, 0)) : 0.0;
@@ -1126,7 +1136,8 @@ PIK_HD double dh_shift(double q, double pm, double d) {
 }
 
 // sin / cos of (theta + d) from sin / cos of theta for a SMALL d (|d| <= 1e-3: the truncated series
-// are exact to < 1e-21): the two line-search evaluations of a gradient step sit at q -+ g with
+// differ from sin d / 1 - cos d by < 1e-21; the results, from sincos_f64's values, are within 2.5e-16 absolute of
+// sin / cos(theta + d): tests/test_gpu_math_accuracy.py, measured 1.7e-16): the two line-search evaluations of a gradient step sit at q -+ g with
 // |g_j| < step size, so their joint angles are the accepted point's angles plus a tiny delta --
 // 13 instructions per joint instead of a full sine / cosine (~38).
 //   sin d = d + d^3 (-1/6 + d^2 / 120),   1 - cos d = d^2 (1/2 - d^2 / 24)
@@ -1633,15 +1644,17 @@ PIK_HD void quat_mul_conj(const double (&a)[4], const double (&b)[4], double (&d
 // atan2(y, x) for y >= 0, x >= 0 -- the only way the path uses it (Eigen angularDistance).
 // fdlibm's atan scheme (breakpoints 7/16, 11/16, 19/16, 39/16; odd minimax polynomial; hi/lo
 // table) with the interval reduction applied to the (y, x) pair so that a single divide serves
-// both the quotient and the reduction; selects only, no divergence.  <= 1 ulp from libm (the
-// verification build; the product build's shorter reduction is described in the function).
+// both the quotient and the reduction; selects only, no divergence.  <= 2 ulp of the true value in the
+// verification build (measured 1.46 ulp); the product build's shorter reduction, described in the function, <= 3 ulp
+// (measured 2.25 ulp): the divide's rounding enters the polynomial's argument, and the reductions add pi/4 / pi/2
+// (tests/test_gpu_math_accuracy.py, y, x in [1e-300, 1e3] and at the reductions' switch points).
 PIK_HD double atan2_pos(MT m, double y, double x) {
 #if !defined(PIK_STRICT) || PIK_XF
     // Product build: two reduction steps instead of fdlibm's four breakpoints -- the smaller over the
     // larger argument (atan2 = pi/2 - atan(x / y) when y > x), then atan(a / b) = pi/4 + atan((a - b) /
     // (a + b)) above tan(pi/8); |r| <= tan(pi/8) < 7/16, so fdlibm's polynomial serves unchanged.  14
     // select instructions instead of 32 (the four-way chains picked among constants, each of which
-    // had to be copied into a vector register first), still one divide; <= 2 ulp from libm.
+    // had to be copied into a vector register first), still one divide; <= 3 ulp (see above).
     const bool sw = y > x;
     const double a = sw ? x : y, b = sw ? y : x; // (selects, not min / max: a NaN stays a NaN)
     const bool t = a > 0.41421356237309503 * b;
@@ -1700,7 +1713,9 @@ PIK_HD double atan2_pos(MT m, double y, double x) {
 #endif
 }
 
-// Eigen angularDistance from the relative quaternion: 2 atan2(|vec|, |w|)
+// Eigen angularDistance from the relative quaternion: 2 atan2(|vec|, |w|); <= 4 ulp of the exact value for the
+// given quaternion (atan2_pos's error plus the rounded norm of the vector part; measured 2.9 ulp for angles in
+// [1e-9, pi], tests/test_gpu_math_accuracy.py)
 PIK_HD double angle_of(MT m, const double (&d)[4], double& vnorm) {
 #if PIK_XF
     vnorm = sqrt_pos(xsumsq3(d[1], d[2], d[3]));

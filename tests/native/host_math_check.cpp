@@ -25,6 +25,10 @@ int run(const ChainHost& h, const pikamd_params& pp, int n, const double* q, con
     // the chain class the exact flavour's kernels pick their form by, and the kinds of the fixed transforms
     std::printf("class %u %x %u\n", c.uniform_z, c.origin_kinds, c.tip_kind);
 #endif
+#if !defined(PIK_STRICT)
+    // the joints whose step is the general constant transform (build_dh): such chains leave the branch-free loop
+    std::printf("dhmask %x\n", c.dh_general_mask);
+#endif
     for (int i = 0; i < n; ++i) {
         double qq[D], sd[D];
         for (int j = 0; j < D; ++j) {

@@ -1,0 +1,221 @@
+"""Solver.fk and Solver.cost of the three libraries -- exact (the default), fast (exact=False: the Denavit-Hartenberg
+kernels) and strict (strict=True) -- against the high-precision reference (tests/hp_reference.py), within bounds from
+error analysis:
+
+  position     <= (8 (D + 2) u + sum_j f_j) R       R = tests/hp_reference.py reach(): the sum of the origin / tip
+  orientation  <= 8 (D + 2) u + sum_j f_j           translations and the prismatic extents; u = 2^-53
+      8 u per step of the chain product: an origin product and a joint product (three-term dot products, <= 3 u each)
+      plus the rounding of the constants and of sin / cos (<= 2 ulp, pik_math.hpp sincos_f64); two more steps for the
+      first origin and the tip.  f_j: 6e-16 for a revolute joint folded by 2 pi (|q_j| > 65536, pik_math.hpp
+      sincos_f64); the fast flavour adds ulp(|q_j| + pi) / 2 for its rounded q_j + theta0 (dh_angle).
+  cost         propagated: 2 s_p^2 |dp| e_p + s_p^2 e_p^2 + the same for the angle (whose error adds the two quaternion
+               extractions and angle_of, 4e-15 rad) + 16 u of the cost
+  verdict      may differ only where |dp| or the angle lies within its error of the threshold
+"""
+import dataclasses
+import math
+
+import numpy as np
+import pytest
+
+import pick_ik_amd as pk
+from pick_ik_amd import robots
+from tests import hp_reference as H
+from tests.test_gpu_fuzz import random_chain
+
+pytestmark = pytest.mark.gpu
+
+U = H.EPS
+FLAVOURS = {"exact": dict(), "fast": dict(exact=False), "strict": dict(strict=True)}
+EXTRACT = 4e-15  # the angle error of matrix_to_quat (<= 5e-16 per component, both frames) + angle_of (4 ulp of pi)
+
+
+def solver(ch, flavour):
+    return pk.Solver(ch, device=0, **FLAVOURS[flavour])
+
+
+def joint_terms(ch, q, flavour):
+    """sum_j f_j of the bound (see the module docstring), per tip path"""
+    f = 0.0
+    for j, t in enumerate(ch.joint_type if not hasattr(ch, "tips") else np.zeros(ch.dof, np.int32)):
+        if int(t) in (robots.PRISMATIC, robots.PLANAR_X, robots.PLANAR_Y):
+            continue
+        if abs(q[j]) > 65536.0:
+            f += 6e-16
+        if flavour == "fast":
+            f += math.ulp(abs(q[j]) + math.pi) / 2
+    return f
+
+
+def fk_bounds(ch, q, flavour):
+    d = max(len(p.variable) for p in H.paths(ch))
+    a = 8 * (d + 2) * U + joint_terms(ch, q, flavour)
+    return a * H.reach(ch, q), a
+
+
+def check_fk(ch, q, flavours=FLAVOURS, what=""):
+    worst = {}
+    for fl in flavours:
+        s = solver(ch, fl)
+        try:
+            got = s.fk(q)
+        finally:
+            s.close()
+        w = 0.0
+        for i in range(len(q)):
+            bp, ba = fk_bounds(ch, q[i], fl)
+            for k, (dp, da, dn) in enumerate(H.pose_errors(ch, q[i], got[i])):
+                assert dp <= bp, (what, fl, i, k, dp, bp, q[i])
+                assert da <= ba, (what, fl, i, k, da, ba, q[i])
+                w = max(w, dp / bp)
+        worst[fl] = w
+    return worst
+
+
+def sample(ch, rng, n):
+    lo = np.where(ch.bounded == 1, ch.qmin, -3.0)
+    hi = np.where(ch.bounded == 1, ch.qmax, 3.0)
+    return rng.uniform(lo, hi, size=(n, ch.dof))
+
+
+@pytest.mark.parametrize("name", ["panda", "ur5", "rr", "panda_on_torso", "torso_dual_arm"])
+def test_fk_robots(name):
+    ch = robots.by_name(name)
+    rng = np.random.default_rng(11)
+    q = sample(ch, rng, 48)
+    # joint values at and just inside the limits
+    q[0], q[1] = ch.qmin, ch.qmax
+    q[2], q[3] = np.nextafter(ch.qmin, ch.qmax), np.nextafter(ch.qmax, ch.qmin)
+    print(name, check_fk(ch, q, what=name))
+
+
+@pytest.mark.parametrize("dof", [1, 2, 7, 10, 11, 16])
+def test_fk_random_chains(dof):
+    rng = np.random.default_rng(500 + dof)
+    ch = random_chain(rng, dof)
+    q = sample(ch, rng, 40)
+    q[0], q[1] = np.where(ch.bounded == 1, ch.qmin, q[0]), np.where(ch.bounded == 1, ch.qmax, q[1])
+    print(dof, check_fk(ch, q, what=f"random chain {dof}"))
+
+
+def test_fk_continuous_joints_across_the_fold():
+    """continuous joints at 1e3 .. 1e6 rad: beyond |q| = 65536 sincos_f64 folds by 2 pi first"""
+    ch = dataclasses.replace(robots.ur5(), bounded=np.zeros(6, np.uint8))
+    rng = np.random.default_rng(12)
+    q = rng.choice([-1.0, 1.0], size=(40, 6)) * 10 ** rng.uniform(3, 6, size=(40, 6))
+    q[:4] = np.array([65536.0, np.nextafter(65536.0, 1e9), -np.nextafter(65536.0, 0), 65536.0 + math.pi])[:, None]
+    print(check_fk(ch, q, what="continuous"))
+
+
+def test_fk_long_prismatic_joints():
+    """prismatic extensions up to 1e3 m"""
+    base = robots.ur5()
+    jt = np.array([0, 1, 0, 1, 0, 0], np.int32)
+    ch = dataclasses.replace(base, joint_type=jt, qmin=np.where(jt == 1, -1e3, base.qmin),
+                             qmax=np.where(jt == 1, 1e3, base.qmax))
+    rng = np.random.default_rng(13)
+    q = sample(ch, rng, 40)
+    q[:, 1] *= 10.0 ** -rng.uniform(0, 4, size=40)
+    print(check_fk(ch, q, what="prismatic"))
+
+
+def perturbed_ur5(eps, variant):
+    """the three variants of tests/test_gpu_fuzz.py test_ill_conditioned_axes_every_shape"""
+    ur5 = robots.ur5()
+    origin = ur5.origin_xyz_rpy.copy()
+    if variant == 0:    # elbow tilted about x against the (parallel) lift axis
+        origin[2, 3] += eps
+    elif variant == 1:  # two consecutive ill-conditioned pairs
+        origin[2, 3] += eps
+        origin[3, 5] -= 0.7 * eps
+    else:               # every joint perturbed a little
+        origin[:, 3:] += eps * np.array([[0.3, -0.2, 0.9]]) * np.arange(1, 7)[:, None]
+    return dataclasses.replace(ur5, origin_xyz_rpy=origin)
+
+
+SWEEP = [1e-15, 1e-14, 1e-13, 5e-13, 9e-13, 1.1e-12, 1e-9, 5e-4, 9e-4, 1.1e-3, 3e-3, 1e-2]
+
+
+def test_ur5_axis_perturbation_sweep():
+    """UR5 with joint axes tilted by eps across both ends of build_dh's general-step window (pik_host.hpp): every
+    flavour within the rounding bound (the fast flavour used to reach 4.3e-13 m just below 1e-12 rad and 7.6e-14 m
+    just above 1e-3 rad)"""
+    rng = np.random.default_rng(14)
+    worst = {}
+    for eps in SWEEP:
+        for variant in range(3):
+            ch = perturbed_ur5(eps, variant)
+            w = check_fk(ch, sample(ch, rng, 24), what=f"eps {eps:g} variant {variant}")
+            worst[eps] = max(worst.get(eps, 0.0), w["fast"])
+    print({k: round(v, 3) for k, v in worst.items()})
+
+
+def rotate(q, angle, axis):
+    """the quaternion q (w x y z) turned by `angle` about the unit `axis` (in double)"""
+    h = angle / 2
+    r = np.concatenate([[math.cos(h)], math.sin(h) * np.asarray(axis)])
+    w1, x1, y1, z1 = q
+    w2, x2, y2, z2 = r
+    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+
+
+def goals_around(ch, q, rng):
+    """goals 1e-12 .. 1e-2 away from the exact frame in position and in angle, at angle pi - 10^-k (near 180 degrees)
+    and 2 pi / 3 (the relative rotation's trace near 0)"""
+    n = len(q)
+    g = np.array([H.pose7(ch, qi) for qi in q])
+    for i in range(n):
+        ax = rng.normal(size=3)
+        ax /= np.linalg.norm(ax)
+        kind = i % 4
+        if kind == 0:
+            g[i, :3] += ax * 10.0 ** rng.uniform(-12, -2)
+        elif kind == 1:
+            g[i, 3:] = rotate(g[i, 3:], 10.0 ** rng.uniform(-12, -2), ax)
+        elif kind == 2:
+            g[i, 3:] = rotate(g[i, 3:], math.pi - 10.0 ** -rng.integers(1, 9), ax)
+        else:
+            g[i, 3:] = rotate(g[i, 3:], 2 * math.pi / 3 + rng.uniform(-1e-6, 1e-6), ax)
+            g[i, :3] += ax * 1e-3
+    return g
+
+
+@pytest.mark.parametrize("name,n", [("panda", 63), ("ur5", 65), ("rr", 257), ("random", 129)])
+def test_cost_and_verdict(name, n):
+    """cost_fn and solution_fn of every flavour against the reference: goals near the frame, near 180 degrees, near
+    trace 0; joint goals on; batch sizes off the multiples of 64 / 256.  The goal quaternion q and -q give the same
+    cost, bit for bit."""
+    rng = np.random.default_rng(15)
+    ch = random_chain(np.random.default_rng(77), 7) if name == "random" else robots.by_name(name)
+    q = sample(ch, rng, n)
+    seed = sample(ch, rng, n)
+    goal = goals_around(ch, q, rng)
+    kw = dict(center_joints_weight=0.05, avoid_joint_limits_weight=0.1, minimal_displacement_weight=0.01,
+              cost_threshold=0.3, position_threshold=3e-3, orientation_threshold=3e-3, position_scale=1.0,
+              rotation_scale=0.5)
+    refs = [H.cost(ch, pk.default_params(**kw), goal[i], seed[i], q[i]) for i in range(n)]
+    neg = goal.copy()
+    neg[:, 3:] *= -1.0
+    for fl in FLAVOURS:
+        p = pk.default_params(**kw)
+        s = solver(ch, fl)
+        try:
+            c, sol = s.cost(p, goal, seed, q)
+            c2, sol2 = s.cost(p, neg, seed, q)
+        finally:
+            s.close()
+        np.testing.assert_array_equal(c, c2, err_msg=f"{fl}: goal quaternion -q")
+        np.testing.assert_array_equal(sol, sol2, err_msg=f"{fl}: goal quaternion -q")
+        for i, r in enumerate(refs):
+            ep, ea = fk_bounds(ch, q[i], fl)
+            ea += EXTRACT
+            lin, ang = float(r.lin[0]), float(r.ang[0])
+            sp2, sr2 = p.position_scale ** 2, p.rotation_scale ** 2
+            tol = (2 * sp2 * lin * ep + sp2 * ep * ep + 2 * sr2 * ang * ea + sr2 * ea * ea
+                   + 16 * U * float(r.cost))
+            assert abs(c[i] - float(r.cost)) <= tol, (fl, i, c[i], float(r.cost), tol)
+            if bool(sol[i]) != r.solution:
+                near = (abs(lin - p.position_threshold) <= ep or abs(ang - p.orientation_threshold) <= ea
+                        or any(abs(float(v) * w * w - p.cost_threshold ** 2) <= 16 * U for w, v in r.goal_terms))
+                assert near, (fl, i, bool(sol[i]), r.solution, lin, ang)

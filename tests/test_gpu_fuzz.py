@@ -328,7 +328,8 @@ def test_fuzz_common_configuration_kernels(built, oracle_mod, i):
         s.close()
 
 
-@pytest.mark.parametrize("eps", [1e-4, 1e-7, 4.9e-12])
+# (2e-15 / 3e-3: pairs near the two ends of build_dh's general-step window, 1e-15 < angle < 0.032 rad)
+@pytest.mark.parametrize("eps", [3e-3, 1e-4, 1e-7, 4.9e-12, 9e-13, 2e-15])
 def test_ill_conditioned_axes_every_shape(built, oracle_mod, eps):
     """Consecutive joint axes that are nearly but not exactly parallel (a URDF that writes 1.57079632679 for
     pi/2): those pairs take a general constant step instead of the Denavit-Hartenberg one

@@ -49,7 +49,7 @@ def run(exe, ch, weights, q, goal, seed):
     r = subprocess.run([exe], input="\n".join(lines), capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = {"fk": [], "cost": [], "grad": [], "sincos": [], "atan2": [], "philox": [], "sincosdelta": [], "class": [],
-           "fkuz": []}
+           "fkuz": [], "dhmask": []}
     for ln in r.stdout.splitlines():
         k, *v = ln.split()
         out[k].append(v)
@@ -176,17 +176,25 @@ def test_fuzz_chains_fast_fk_on_host(oracle_mod):
         assert (np.abs(g[:, :, 0] - g[:, :, 1]) / scale).max() < 1e-6, f"case {i}"
 
 
-@pytest.mark.parametrize("eps", [1e-3, 1e-5, 1e-7, 1e-9, 4.9e-12, 3e-12, 1e-13])
+# (across both ends of build_dh's general-step window, 1e-15 < angle < 0.032 rad: pairs just outside it are taken as
+# parallel / as skew, pairs just inside get the general step)
+NEAR_PARALLEL_EPS = [1e-15, 1e-14, 1e-13, 5e-13, 9e-13, 1.1e-12, 3e-12, 4.9e-12, 1e-9, 1e-7, 1e-5, 5e-4, 9e-4, 1e-3,
+                     1.1e-3, 3e-3, 1e-2, 3e-2, 3.3e-2, 5e-2, 0.2]
+
+
+@pytest.mark.parametrize("eps", NEAR_PARALLEL_EPS)
 def test_nearly_parallel_axes_fast_fk_on_host(oracle_mod, eps):
     """Consecutive joint axes that are nearly but not exactly parallel (a URDF that writes
     1.57079632679 for pi/2 is 4.9e-12 rad off): the common normal of such a pair lies ~L / angle away,
     so the plain Denavit-Hartenberg construction lost 1e-16 L / angle of FK accuracy (3e-5 m at
-    3e-12 rad).  build_dh gives these pairs a general constant step; FK must stay within 1e-12."""
+    3e-12 rad).  build_dh gives these pairs a general constant step; FK must stay within 1e-12 of the oracle and
+    within the rounding bound of the exact FK (tests/hp_reference.py; the bound of tests/test_gpu_fk_accuracy.py)."""
     import dataclasses
+    from tests import hp_reference as H
     O = oracle_mod
     exe = build(False)
     ur5 = robots.ur5()
-    worst = 0.0
+    worst = worst_hp = 0.0
     for variant in range(3):
         origin = ur5.origin_xyz_rpy.copy()
         if variant == 0:    # elbow tilted about x against the (parallel) lift axis
@@ -206,13 +214,53 @@ def test_nearly_parallel_axes_fast_fk_on_host(oracle_mod, eps):
         ofk = o.fk(q)
         worst = max(worst, np.abs(fk[:, :3] - ofk[:, :3]).max())
         np.testing.assert_allclose(fk[:, :3], ofk[:, :3], rtol=0, atol=1e-12, err_msg=f"variant {variant}")
+        # against the exact FK: c D u R plus the rounding of q + theta0 (|theta0| <= pi)
+        for i in range(0, len(q), 4):
+            (dp, da, _), = H.pose_errors(ch, q[i], fk[i])
+            dq = sum(math.ulp(abs(x) + math.pi) / 2 for x in q[i])
+            assert dp <= fk_bound(ch) + dq * H.reach(ch), (variant, i, dp)
+            assert da <= fk_bound(ch, angle=True) + dq, (variant, i, da)
+            worst_hp = max(worst_hp, dp / (fk_bound(ch) + dq * H.reach(ch)))
         sgn = np.sign((fk[:, 3:] * ofk[:, 3:]).sum(axis=1, keepdims=True))
         np.testing.assert_allclose(fk[:, 3:] * sgn, ofk[:, 3:], rtol=0, atol=1e-12)
         # the frame-based probes still see the right joint axes
         g = np.array(out["grad"], dtype=float).reshape(len(q), ch.dof, 2)
         scale = np.abs(g[:, :, 1]).max(axis=1, keepdims=True) + 1e-300
         assert (np.abs(g[:, :, 0] - g[:, :, 1]) / scale).max() < 1e-6
-    print(f"eps {eps:g}: worst FK position error {worst:.2e} m")
+    print(f"eps {eps:g}: worst FK position error {worst:.2e} m, {worst_hp:.3f} of the rounding bound")
+
+
+def fk_bound(ch, angle=False):
+    """rounding bound of a double-precision FK (tests/test_gpu_fk_accuracy.py): 8 (D + 2) u per step of the chain
+    product (origin and joint products: <= 3 u each for the three-term dot products, plus the rounding of the constants
+    and of sin / cos), times the reach R for a position"""
+    from tests import hp_reference as H
+    b = 8 * (ch.dof + 2) * H.EPS
+    return b if angle else b * H.reach(ch)
+
+
+@pytest.mark.parametrize("name", ["panda", "ur5", "rr", "panda_on_torso", "dual_ur5", "torso_dual_arm",
+                                  "floating_panda"])
+def test_robots_keep_the_branch_free_fast_fk(name):
+    """No robot of pick_ik_amd.robots -- and with them no chain bench.py measures -- has a pair of joint axes in
+    build_dh's general-step window: the fast flavour's FK of every benchmarked chain stays the branch-free loop
+    (ChainK::dh_general_mask = 0; the kernels for the common configuration are eligible)."""
+    ch = robots.by_name(name)
+    exe = build(False)
+    if hasattr(ch, "tips"):  # every tip path as a serial chain of its own (build_dh works path by path)
+        import dataclasses
+        serial = []
+        for k, t in enumerate(ch.tips):
+            v = t.variable
+            serial.append(robots._chain(f"{name}_{k}", t.origin_xyz_rpy, t.axis, t.tip_xyz_rpy, ch.qmin[v], ch.qmax[v],
+                                        ch.vmax[v], bounded=ch.bounded[v], joint_type=t.joint_type))
+    else:
+        serial = [ch]
+    for c in serial:
+        q = np.clip(np.zeros((1, c.dof)), c.qmin, c.qmax)
+        goal = np.array([[0, 0, 0, 1.0, 0, 0, 0]])
+        out = run(exe, c, (0.0, 0.0, 0.0), q, goal, q)
+        assert int(out["dhmask"][0][0], 16) == 0, (c.name, out["dhmask"])
 
 
 @pytest.mark.parametrize("compiler", ["g++", CLANG], ids=["gcc", "clang"])
@@ -263,3 +311,13 @@ def test_chain_classes_and_their_sparse_products_on_host(oracle_mod, compiler):
         if cls:
             np.testing.assert_array_equal(np.array(out["fkuz"], dtype=float), ofk, err_msg=f"{name} class {cls} fk_uz")
     assert seen >= {1, 2}
+
+
+@pytest.mark.parametrize("flavour", ["fast", "exact_fma", "strict"])
+def test_math_accuracy_host_half(flavour):
+    """The host half of tests/test_gpu_math_accuracy.py: the same sweep of sincos_f64, fold_2pi, sincos_delta,
+    atan2_pos, angle_of and matrix_to_quat (2 x 10^5 points per range) compiled for the host, against long double and
+    mpmath, within the bounds written beside the functions (pik_math.hpp)."""
+    from tests import test_gpu_math_accuracy as A
+    seen = A.check(flavour, A.run(A.build(flavour, device=False), 200000, 300), device=False)
+    assert len(seen) == 24, sorted(seen)
