@@ -111,9 +111,22 @@ int check_solver(const pikamd_solver* s) {
     for (int k = 1; k < s->n_tips; ++k) f = f || s->more[k - 1].float_mask != 0u || s->more[k - 1].n_mimic != 0;
     return f;
 }
-const pik::LaunchOps* ops_of(const pikamd_solver* s) {
+// ... and for a gradient step: the Denavit-Hartenberg kernels' probes (pik_math.hpp probe_joint) take the arcsine of
+// a half-angle difference as a 4-term series, exact to rounding for gd_step_size <= 1e-2 and 1e-12 .. 1e-4 of the
+// gradient off at 0.1 .. 1 (tests/test_gpu_step_accuracy.py).  A larger step is served by the literal kernels, which
+// take the central differences as the reference does.  (Measured: an exact arcsine inside probe_joint -- the
+// arctangent form behind a ParamsK flag -- grew the spilled scalar registers of 10 of the 44 general kernels of
+// lengths 2 and 3 past profiles/r06_kernel_resources.csv, e.g. memetic_kernel<2,2,false,1> 192 -> 210 and
+// gd_step_kernel<3,false> 54 -> 62; loading the flag at its use, keying it on line_delta or selecting by |x| grew
+// them as well, and a non-inlined arcsine added 32 bytes of scratch per lane.)
+[[maybe_unused]] bool needs_literal(const pikamd_solver* s, const pikamd_params* p) {
+    return needs_literal(s) || (p && p->gd_step_size > 1.0e-2);
+}
+const pik::LaunchOps* ops_of(const pikamd_solver* s, const pikamd_params* p = nullptr) {
 #if !defined(PIK_STRICT)
-    if (needs_literal(s)) return literal_ops(s->chain.dof);
+    if (needs_literal(s, p)) return literal_ops(s->chain.dof);
+#else
+    (void)p;
 #endif
     return pik::launch_ops(s->chain.dof);
 }
@@ -142,10 +155,9 @@ const pik::LaunchOps* solve_ops_of(const pikamd_solver* s, const pikamd_params* 
     if (common_eligible(s, p, pk))
         if (const pik::LaunchOps* o = common_ops(s->chain.dof, pk.goal_mask != 0)) return o;
 #else
-    (void)p;
     (void)pk;
 #endif
-    return ops_of(s);
+    return ops_of(s, p);
 }
 
 int no_kernels(int dof) {
@@ -449,7 +461,7 @@ int32_t pikamd_gd_step_batch(pikamd_solver* s, const pikamd_params* p, int64_t n
     HIP_TRY(hipMemcpy(s->stage[3].p, best, sz[3], hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->stage[4].p, local_cost, sz[4], hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->stage[5].p, best_cost, sz[5], hipMemcpyHostToDevice));
-    if (int rc = ops_of(s)->step(s, pk, n, (const double*)s->stage[0].p, (const double*)s->stage[1].p,
+    if (int rc = ops_of(s, p)->step(s, pk, n, (const double*)s->stage[0].p, (const double*)s->stage[1].p,
                                  (double*)s->stage[2].p, (double*)s->stage[3].p, (double*)s->stage[4].p,
                                  (double*)s->stage[5].p, (double*)s->stage[6].p, (int*)s->stage[7].p, nullptr))
         return rc;
@@ -1009,7 +1021,7 @@ int32_t pikamd_self_test(pikamd_solver* s, const pikamd_params* p, int32_t n, ui
     if (n < 1 || n > 4096) return fail(PIKAMD_EINVAL, "n out of range [1, 4096]");
     // the flavour under test: the exact kernels (this library is the verification build, the option "arithmetic" =
     // exact, or a chain only they serve) or the product flavours' -- each keeps its own mask of switched-off widths
-    const bool exact_now = pik::EXACT_FLAVOUR || s->opt.exact || needs_literal(s);
+    const bool exact_now = pik::EXACT_FLAVOUR || s->opt.exact || needs_literal(s, p);
     auto mask_of = [exact_now](pik::SolverOptions& o) -> unsigned& { return exact_now ? o.disabled_lanes_exact : o.disabled_lanes; };
     if (disabled_out) *disabled_out = mask_of(s->opt);
     const int d = s->chain.dof, tips = s->n_tips;
@@ -1164,7 +1176,7 @@ static int maybe_self_test(pikamd_solver* s, const pikamd_params* p) {
     // the line-search form and the approximate-solution return -- thresholds, weights, population and budgets do not,
     // so a plugin whose parameters change at run time does not pay again.
     unsigned long long h = 1469598103934665603ull;
-    const long long key[] = {s->opt.exact ? 1 : 0, p->mode, p->mode == 0 ? p->memetic_num_threads : 1,
+    const long long key[] = {needs_literal(s, p) ? 1 : 0, p->mode, p->mode == 0 ? p->memetic_num_threads : 1,
                              p->mode == 0 ? p->memetic_elite_size : 0, pk.goal_mask, pk.line_delta, pk.approx,
                              pk.has_pos_thr, pk.has_ori_thr, pk.stop_on_valid, pk.stop_on_first,
                              p->position_scale > 0.0 ? 1 : 0, p->rotation_scale > 0.0 ? 1 : 0}; // (the pose cost's two terms)
@@ -1207,7 +1219,7 @@ const char* pikamd_kernel_name(const pikamd_solver* s, const pikamd_params* p) {
     ns = "pik_strict";
 #else
     pik::ParamsK pk;
-    if (needs_literal(s)) ns = "pik_exact";
+    if (needs_literal(s, p)) ns = "pik_exact";
     else if (!pik::make_params_k(p, pk) && common_eligible(s, p, pk) && common_ops(s->chain.dof, pk.goal_mask != 0))
         ns = pk.goal_mask != 0 ? "pik_common_goals" : "pik_common";
 #endif

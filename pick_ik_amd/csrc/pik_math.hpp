@@ -1919,7 +1919,7 @@ PIK_HD void eval_pose_sc(CK<D> c_in, PK p_in, const GoalK& g, const double (&see
 //   position   |dp|^2 - |dm|^2 = 4 su (mid . u)            with dp/dm = mid +- su u
 //   rotation   the half angles alpha(+-) = atan2(|v(+-)|, |w(+-)|) differ from the base alpha0 by
 //              delta(+-) = asin((|v(+-)| |w0| - |v0| |w(+-)|) / |d0|^2)   (sine of a difference;
-//              |delta| <= h/2, so the arcsine is a 4-term series), and
+//              |delta| <= h/2, so the arcsine is a 4-term series: h <= 1e-2 only, see below), and
 //              (2 rs alpha+)^2 - (2 rs alpha-)^2 = 4 rs^2 (delta+ - delta-)(2 alpha0 + delta+ + delta-)
 //   joint goals only joint j's term changes: w (tp^2 - tm^2)
 // Same mathematics as the literal central difference, no cancellation of two O(1) costs, and no
@@ -1999,7 +1999,8 @@ PIK_HD double probe_joint(PK p, const EvalOut& base, const ProbeBase& pb, const 
         const double sp = (sqrt_pos(vp2) * pb.aw0 - base.vn * fabs(wp)) * pb.inv_n2;
         const double sm = (sqrt_pos(vm2) * pb.aw0 - base.vn * fabs(wm)) * pb.inv_n2;
         // asin x = x + x^3/6 + 3x^5/40 + 15x^7/336 (|x| <= sin(h/2): the next term is < 1e-16
-        // relative for every step size up to 1e-2)
+        // relative for every step size up to 1e-2; it grows as h^8 above, 8e-9 of the gradient at h = 0.3,
+        // and the library serves a larger step by the literal kernels, pik_amd.hip needs_literal)
         const double sp2 = sp * sp, sm2 = sm * sm;
         const double dp = sp + sp * sp2 * (1.0 / 6.0 + sp2 * (3.0 / 40.0 + sp2 * (15.0 / 336.0)));
         const double dm = sm + sm * sm2 * (1.0 / 6.0 + sm2 * (3.0 / 40.0 + sm2 * (15.0 / 336.0)));

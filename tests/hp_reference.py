@@ -17,8 +17,12 @@ kernels and the oracle share (a sine, an arctangent, a quaternion extraction) sh
 Floating and mimic joints are not modelled: chains with them stay with the oracle (oracle/pik_oracle.c), whose
 literal chain product the exact flavours match bit for bit.
 
-The inputs are doubles and are taken as exact; the goal quaternion is normalised here (Eigen's toRotationMatrix
-assumes a unit quaternion; a double-rounded one is off by ~1e-16, which the callers' bounds absorb).
+  step(chain, params, goal, seed, q)  step() of src/ik_gradient.cpp:24-94 taken literally, every cost by `cost`: the
+                                      raw and normalised gradient, the line search and the clamped update (`Step`)
+
+The inputs are doubles and are taken as exact, the goal quaternion included: it goes through Eigen's
+toRotationMatrix and back as upstream's does (`goal_quat`), so a goal quaternion off unit norm gives upstream's
+angle, not that of the normalised quaternion.
 """
 from __future__ import annotations
 
@@ -170,9 +174,37 @@ def quat_angle(qa, qb):
     return 2 * M.atan2(M.sqrt(d[1] ** 2 + d[2] ** 2 + d[3] ** 2), abs(d[0]))
 
 
-def angular_distance(R, goal_quat):
-    """Eigen angularDistance between the exact frame R and the goal quaternion (w, x, y, z; normalised here)"""
-    return quat_angle(matrix_to_quat(R), unit(goal_quat))
+def goal_quat(gq):
+    """the goal quaternion as upstream sees it: tf2::fromMsg builds the goal frame's matrix with Eigen's
+    toRotationMatrix, which does not normalise (a quaternion of norm s gives s^2 R + (1 - s^2) I), and
+    angular_distance re-derives a quaternion from that matrix (src/goal.cpp:22-23) by Eigen's branches (the trace
+    when it is > 0, else the largest diagonal entry) -- not a multiple of the given one unless it is unit"""
+    w, x, y, z = (mpf(v) for v in gq)
+    R = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+    tr = R[0][0] + R[1][1] + R[2][2]
+    if tr > 0:
+        t = M.sqrt(tr + 1)
+        return [t / 2, (R[2][1] - R[1][2]) / (2 * t), (R[0][2] - R[2][0]) / (2 * t), (R[1][0] - R[0][1]) / (2 * t)]
+    i = 0
+    if R[1][1] > R[0][0]:
+        i = 1
+    if R[2][2] > R[i][i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = M.sqrt(R[i][i] - R[j][j] - R[k][k] + 1)
+    v = [M.mpf(0)] * 3
+    v[i] = t / 2
+    v[j] = (R[j][i] + R[i][j]) / (2 * t)
+    v[k] = (R[k][i] + R[i][k]) / (2 * t)
+    return [(R[k][j] - R[j][k]) / (2 * t)] + v
+
+
+def angular_distance(R, gq):
+    """Eigen angularDistance between the exact frame R and the goal quaternion (w, x, y, z) as upstream takes it
+    (`goal_quat`); angularDistance itself does not depend on the norm of either quaternion"""
+    return quat_angle(matrix_to_quat(R), goal_quat(gq))
 
 
 def linear_distance(t, goal_t):
@@ -290,3 +322,72 @@ def pose_errors(chain, q, pose):
         ang = quat_angle([x / n for x in qp], qe)
         out.append((dp, float(ang), float(abs(n - 1))))
     return out
+
+
+@dataclasses.dataclass
+class LineSearch:
+    G_line: np.ndarray  # the gradient the line search ran with (doubles)
+    line: tuple         # (Cost at fl(q - G_line), Cost at fl(q + G_line))
+    p1: object          # their costs (mpf)
+    p3: object
+    p2: object          # (p1 + p3) / 2
+    cost_diff: object   # (p3 - p1) / 2
+    joint_diff: object  # p2 / cost_diff, 0 where that is not finite
+    local: list         # clamp(q - G_line joint_diff), exact (mpf)
+
+
+@dataclasses.dataclass
+class Step:
+    base: Cost          # cost at q
+    probes: list        # per joint: (Cost at fl(q_j - h), Cost at fl(q_j + h))
+    raw: list           # per joint: p3 - p1 of the probes (mpf)
+    probe_width: list   # per joint: fl(q_j + h) - fl(q_j - h) (mpf, exact)
+    f: object           # h / (h + sum |raw|) (mpf)
+    G: list             # the normalised gradient raw * f (mpf)
+    ls: LineSearch      # from the given G, or from G rounded to doubles
+    local_cost: object  # cost at ls.local rounded to doubles (mpf)
+
+
+def clamp(chain, j, v):
+    """Variable::clamp_to_limits, src/robot.cpp:36-42 (an unbounded variable is left as it is)"""
+    if int(chain.bounded[j]) == 0:
+        return v
+    lo, hi = mpf(chain.qmin[j]), mpf(chain.qmax[j])
+    return lo if v < lo else hi if hi < v else v
+
+
+def line_search(chain, params, goal, seed, q, G):
+    """the second half of step(), src/ik_gradient.cpp:56-81, from the double gradient G: costs at the doubles
+    fl(q -+ G), joint_diff = p2 / cost_diff (0 where not finite), the clamped update (exact)"""
+    q, G = np.asarray(q, dtype=np.float64), np.asarray(G, dtype=np.float64)
+    line = (cost(chain, params, goal, seed, q - G), cost(chain, params, goal, seed, q + G))
+    p1, p3 = line[0].cost, line[1].cost
+    p2 = (p1 + p3) / 2
+    cd = (p3 - p1) / 2
+    jd = p2 / cd if cd != 0 else M.mpf(0)
+    local = [clamp(chain, j, mpf(q[j]) - mpf(G[j]) * jd) for j in range(len(q))]
+    return LineSearch(G, line, p1, p3, p2, cd, jd, local)
+
+
+def step(chain, params, goal, seed, q, G=None):
+    """step() of src/ik_gradient.cpp:24-94 taken literally, every cost at PREC bits (`cost`): the probes at the
+    doubles fl(q_j +- h), the gradient raw_j = p3 - p1 normalised by f = h / (h + sum |raw|), then `line_search`.
+    `G` (doubles): run the line search from this gradient instead of the reference's own (rounded to doubles), so
+    that it can be checked from a kernel's returned gradient separately from the gradient stage."""
+    q = np.asarray(q, dtype=np.float64)
+    h = float(params.gd_step_size)
+    c = lambda x: cost(chain, params, goal, seed, x)  # noqa: E731
+    base = c(q)
+    probes, raw, width = [], [], []
+    for j in range(len(q)):
+        lo, hi = q.copy(), q.copy()
+        lo[j] = q[j] - h  # (double arithmetic: the reference's working[i] = local[i] -+ step_size)
+        hi[j] = q[j] + h
+        probes.append((c(lo), c(hi)))
+        raw.append(probes[-1][1].cost - probes[-1][0].cost)
+        width.append(mpf(hi[j]) - mpf(lo[j]))
+    hh = mpf(h)
+    f = hh / (hh + sum(abs(g) for g in raw))
+    Gm = [g * f for g in raw]
+    ls = line_search(chain, params, goal, seed, q, np.array([float(g) for g in Gm]) if G is None else G)
+    return Step(base, probes, raw, width, f, Gm, ls, c(np.array([float(x) for x in ls.local])).cost)

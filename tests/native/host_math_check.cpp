@@ -90,7 +90,7 @@ int run(const ChainHost& h, const pikamd_params& pp, int n, const double* q, con
 }
 
 int main(int argc, char** argv) {
-    // stdin: dof n ; chain arrays ; params subset ; then n x (q[dof] goal[7] seed[dof])
+    // stdin: dof n ; chain arrays ; params subset (three goal weights, gd_step_size) ; then n x (q[dof] goal[7] seed[dof])
     int dof, n;
     if (std::scanf("%d %d", &dof, &n) != 2) return 2;
     std::vector<double> o(6 * dof), ax(3 * dof), tip(6), lo(dof), hi(dof), vm(dof);
@@ -103,14 +103,15 @@ int main(int argc, char** argv) {
     ChainHost h;
     if (const char* m = build_chain(&ch, h)) { std::fprintf(stderr, "%s\n", m); return 1; }
     pikamd_params pp;
-    // defaults (src/pick_ik_parameters.yaml) + the three goal weights from stdin
+    // defaults (src/pick_ik_parameters.yaml) + the three goal weights and the step size from stdin
     pp.mode = 1; pp.gd_step_size = 1e-4; pp.gd_max_iters = 100; pp.gd_min_cost_delta = 1e-12;
     pp.position_threshold = 1e-3; pp.orientation_threshold = 1e-3; pp.cost_threshold = 1e-3;
     pp.position_scale = 1.0; pp.rotation_scale = 0.5;
     pp.stop_optimization_on_valid_solution = 1; pp.memetic_num_threads = 1; pp.memetic_stop_on_first_solution = 1;
     pp.memetic_population_size = 16; pp.memetic_elite_size = 4; pp.memetic_wipeout_fitness_tol = 1e-5;
     pp.memetic_max_generations = 100; pp.memetic_gd_max_iters = 25; pp.return_approximate_solution = 0;
-    if (std::scanf("%lf %lf %lf", &pp.center_joints_weight, &pp.avoid_joint_limits_weight, &pp.minimal_displacement_weight) != 3) return 2;
+    if (std::scanf("%lf %lf %lf %lf", &pp.center_joints_weight, &pp.avoid_joint_limits_weight,
+                   &pp.minimal_displacement_weight, &pp.gd_step_size) != 4) return 2;
     std::vector<double> q(n * dof), goal(n * 7), seed(n * dof);
     for (int i = 0; i < n; ++i) {
         for (int j = 0; j < dof; ++j) if (std::scanf("%lf", &q[i * dof + j]) != 1) return 2;

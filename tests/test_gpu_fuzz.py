@@ -377,3 +377,34 @@ def test_ill_conditioned_axes_every_shape(built, oracle_mod, eps):
                     assert is_sol[0] == 1 and abs(c[0] - cost[b]) <= 1e-9 * max(1.0, abs(c[0]))
         finally:
             s.close()
+
+
+@pytest.mark.parametrize("i", range(8))
+def test_fuzz_fast_large_step_shape_invariance(built, i):
+    """make_case(i) with gd_step_size = 0.3 on a fast handle: above the range of the fast probes' arcsine series
+    (pik_math.hpp probe_joint) the literal kernels serve the call (pik_amd.hip needs_literal).  The same answers for
+    1, 2, 4, 8 and 16 lanes per elite and the compaction marks, and every SUCCESS passes the reference's solution test
+    (tests/hp_reference.py, 128 bits)"""
+    from tests import hp_reference as H
+    ch, kw, q, seed, rs, off = make_case(i)
+    kw = dict(kw, gd_step_size=0.3)
+    s = pk.Solver(ch, device=0, exact=False)
+    try:
+        goal = s.fk(q)
+        p = pk.default_params(**kw)
+        assert s.kernel_name(p).startswith("pik_exact::"), s.kernel_name(p)
+        outs, names = [], []
+        for lanes, marks in ((1, "none"), (2, "1,3"), (4, "none"), (4, "2,3"), (8, "1,2,4,7"), (16, "none"),
+                             (None, None)):
+            s.set_option("lanes_per_elite", lanes)
+            s.set_option("passes", marks)
+            outs.append(s.solve_batch(p, goal, seed, rng_seed=rs, problem_offset=off))
+            names.append(f"lanes {lanes} marks {marks}")
+    finally:
+        s.close()
+    for other, name in zip(outs[1:], names[1:]):
+        for x, y, w in zip(outs[0], other, ("solution", "status", "cost", "stats")):
+            np.testing.assert_array_equal(x, y, err_msg=f"case {i} {kw} [{names[0]}] vs [{name}] {w}")
+    sol, st, _, _ = outs[0]
+    for b in np.flatnonzero(st == pk.SUCCESS)[:16]:
+        assert H.cost(ch, p, goal[b], seed[b], sol[b]).solution, f"case {i} problem {b}: SUCCESS, reference rejects"

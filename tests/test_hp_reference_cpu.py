@@ -140,3 +140,73 @@ def test_minimal_displacement_factors_and_joint_goals(oracle_mod):
         r = H.cost(ch, p, goal, seed, q)
         assert float(r.cost) == pytest.approx(c[0], rel=1e-12)
         assert r.solution == bool(sol[0])
+
+
+@pytest.mark.parametrize("mode", ["libm", "portable", "fma"])
+@pytest.mark.parametrize("name,h", [("panda", 1e-4), ("ur5", 1e-12), ("rr", 0.3), ("random_8", 3e-2)])
+def test_step_agrees_with_the_oracle(oracle_mod, mode, name, h):
+    """hp_reference.step against the oracle's literal step() (pko_gd_step_batch) in its three math modes: the
+    normalised gradient, the update from the oracle's own gradient and the cost there within the bounds of
+    tests/test_gpu_step_accuracy.py for an exact flavour (the oracle's chain product: 8 (D + 2) u per step)"""
+    from tests import test_gpu_step_accuracy as S
+    O = oracle_mod
+    ch = random_chain(np.random.default_rng(908), 8) if name == "random_8" else robots.by_name(name)
+    o = O.Oracle(ch)
+    rng = np.random.default_rng(31)
+    n = 6
+    lo = np.where(ch.bounded == 1, ch.qmin, -3.0)
+    hi = np.where(ch.bounded == 1, ch.qmax, 3.0)
+    q = rng.uniform(lo, hi, size=(n, ch.dof))
+    seed = rng.uniform(lo, hi, size=(n, ch.dof))
+    with O.math_mode(mode):
+        goal = o.fk(rng.uniform(lo, hi, size=(n, ch.dof)))
+        p = O.default_params(gd_step_size=h, center_joints_weight=0.05, avoid_joint_limits_weight=0.1,
+                             minimal_displacement_weight=0.02)
+        lc = np.array([o.cost(p, goal[i], seed[i], q[i])[0][0] for i in range(n)])
+        local, best, lc2, bc, G, imp = o.gd_step(p, goal, seed, q, q, lc, lc)
+    asserted = 0
+    for i in range(n):
+        st = H.step(ch, p, goal[i], seed[i], q[i], G=G[i])
+        eg = S.gradient_bounds(ch, p, "exact", q[i], seed[i], st)
+        eG = S.normalised_bounds(st, eg, h)
+        assert (np.abs(G[i] - [float(x) for x in st.G]) <= eG).all(), (name, mode, i)
+        ep2, ecd = S.line_bounds(ch, p, "exact", q[i], st.ls, 1)
+        cd, jd = abs(float(st.ls.cost_diff)), abs(float(st.ls.joint_diff))
+        if cd > 2 * ecd:
+            asserted += 1
+            ejd = (ep2 + jd * ecd) / (cd - ecd) + 2 * U * jd
+            eq = np.abs(G[i]) * ejd + 2 * U * (np.abs(q[i]) + np.abs(G[i]) * jd)
+            assert (np.abs(local[i] - [float(x) for x in st.ls.local]) <= eq).all(), (name, mode, i)
+        r = H.cost(ch, p, goal[i], seed[i], local[i])
+        assert abs(lc2[i] - float(r.cost)) <= S.cost_bound(ch, p, "exact", local[i], r), (name, mode, i)
+    assert asserted >= n // 2, (name, mode, asserted)
+
+
+def test_off_unit_goal_quaternions_agree_with_the_oracle(oracle_mod):
+    """hp_reference.goal_quat -- a goal quaternion off unit norm taken as upstream takes it (tf2::fromMsg's
+    toRotationMatrix, which does not normalise, then Quaterniond(matrix) by Eigen's branches) -- against the oracle,
+    whose make_goal restates the same path: the cost agrees to rounding, on both of Eigen's branches (trace > 0 and
+    the largest diagonal entry), while the normalised quaternion would give another cost"""
+    O = oracle_mod
+    ch = robots.panda()
+    o = O.Oracle(ch)
+    rng = np.random.default_rng(43)
+    n = 24
+    q = rng.uniform(ch.qmin, ch.qmax, size=(n, ch.dof))
+    goal = np.array([H.pose7(ch, x) for x in rng.uniform(ch.qmin, ch.qmax, size=(n, ch.dof))])
+    goal[:, 3:] *= np.array([1.1, 0.9, 1 + 1e-3, 1 - 1e-3, 1 + 1e-6, 1 - 1e-6] * 4)[:, None]
+    p = O.default_params()
+    branches, differs = set(), 0
+    for i in range(n):
+        w, x, y, z = goal[i, 3:]
+        branches.add(3 - 4 * (x * x + y * y + z * z) > 0)  # the trace of toRotationMatrix
+        with O.math_mode("libm"):
+            c = o.cost(p, goal[i], q[i], q[i])[0][0]
+        r = H.cost(ch, p, goal[i], q[i], q[i])
+        assert float(r.cost) == pytest.approx(c, rel=1e-12), (i, float(r.cost), c)
+        (t, R), = H.fk(ch, q[i])
+        unit = H.pose_cost(H.linear_distance(t, goal[i, :3]), H.quat_angle(H.matrix_to_quat(R), H.unit(goal[i, 3:])),
+                           p.position_scale, p.rotation_scale)
+        differs += abs(float(unit) - c) > 1e-9 * c
+    assert branches == {True, False}, branches
+    assert differs >= 8, differs
