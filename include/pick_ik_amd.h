@@ -440,6 +440,57 @@ const char* pikamd_version(void);
  * in libpick_ik_amd_strict.so) -- for matching rocprof rows, and for tests that must know which ran */
 const char* pikamd_kernel_name(const pikamd_solver* s, const pikamd_params* p);
 
+/* ---- Cartesian waypoint paths: chained local IK ---------------------------------------------
+ * What MoveIt's computeCartesianPath, servoing and straight-line approach sampling do with local mode
+ * (p->mode must be 1): P paths of W waypoints each, every waypoint solved from the previous waypoint's
+ * answer, a path stopping at its first failure.  One kernel launch walks all waypoints of all paths on the
+ * device; the previous answer becomes the next seed in registers.  The result is DEFINED as what this loop of
+ * pikamd_solve_batch calls returns, bit for bit:
+ *
+ *   seed[p] = start[p]; held[p] = true; reached[p] = 0
+ *   for k in 0 .. W-1:
+ *     for every p with held[p]:
+ *       (sol, st, cost, stats) = pikamd_solve_batch(local mode, goal[p][k], seed = initial guess = seed[p])
+ *       jump = st > 0 and max_joint_step given and any j: |sol[j] - seed[p][j]| > max_joint_step[j]
+ *              (an entry of max_joint_step that is 0 or less, or not a number, sets no limit for its variable)
+ *       if st > 0 and not jump: solution[p][k] = sol; status[p][k] = st; seed[p] = sol; reached[p] += 1
+ *       else: solution[p][k] = seed[p]; status[p][k] = jump ? PIKAMD_PATH_JUMP : st; held[p] = false
+ *       final_cost[p][k] = cost; stats[p][k] = stats      (what the call returned, also for a refused jump)
+ *     for every p not held before this k:
+ *       solution[p][k] = seed[p]; status[p][k] = PIKAMD_NOT_ATTEMPTED; final_cost[p][k] = 0; stats[p][k] = zero
+ *
+ * st > 0 covers PIKAMD_SUCCESS and PIKAMD_APPROXIMATE: with return_approximate_solution set (servoing) a path
+ * never stops on a solver failure.  seed[p] is both the start of the search and the minimal-displacement
+ * reference.  Local mode draws no random numbers: there is no rng_seed.  reached[p] / W is
+ * computeCartesianPath's fraction.
+ *   goal_pos_quat [P][W][n_tips][7], start [P][dof], max_joint_step [dof] (may be NULL),
+ *   solution [P][W][dof], status [P][W], final_cost [P][W] (may be NULL), stats [P][W] (may be NULL),
+ *   reached [P] (may be NULL).
+ * Not with the option joint_layout = soa. */
+#define PIKAMD_NOT_ATTEMPTED 0   /* status of a waypoint behind the one its path stopped at */
+#define PIKAMD_PATH_JUMP (-1001) /* the waypoint was solved, but a variable moved further than max_joint_step
+                                    allows (outside the values of MoveItErrorCodes) */
+/* [host-api-begin] Entry points added after the committed kernel profiles were taken.  They are host functions: the
+ * hash of a kernel flavour's DEVICE source (pick_ik_amd/build.py flavour_sha) leaves the declarations between this
+ * comment and the matching end comment out, so that adding host API does not mark the profiles of untouched kernels stale. */
+/* host pointers; synchronous, staged through the library's own pinned buffers and stream like
+ * pikamd_solve_batch, behind the same automatic self test of the local-mode kernels */
+int32_t pikamd_solve_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                           const double* goal_pos_quat, const double* start, const double* max_joint_step,
+                           double* solution, int32_t* status, double* final_cost, pikamd_stats* stats,
+                           int32_t* reached);
+/* device pointers (max_joint_step too); enqueues on `stream` and returns without synchronising, no self test
+ * (see pikamd_solve_batch_device for `slot`) */
+int32_t pikamd_solve_paths_device(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                  const double* d_goal_pos_quat, const double* d_start,
+                                  const double* d_max_joint_step, double* d_solution, int32_t* d_status,
+                                  double* d_final_cost, pikamd_stats* d_stats, int32_t* d_reached,
+                                  void* stream, int32_t slot);
+/* name of the kernel pikamd_solve_paths* launches for P paths (see pikamd_kernel_name), e.g.
+ * `pik_exact::ik_path_team_kernel<7,16>` */
+const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
+/* [host-api-end] */
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@ The library is one translation unit for the C ABI (pik_amd.hip) plus one per sup
 (pik_inst.hip compiled with -DPIK_INST_D=1..16): the kernels are templates over the number of
 joints, and a single translation unit took 2.5 minutes; the seventeen objects build in parallel and
 only the ones whose inputs changed are rebuilt.  Objects live in pick_ik_amd/_build/ (git-ignored).
+The waypoint-path kernels (pik_path_inst.hip) are translation units of their own, one per chain length for the
+flavours fast, exact and strict (_path_objects).
 """
 from __future__ import annotations
 
@@ -23,7 +25,7 @@ LIB = os.path.join(_HERE, "libpick_ik_amd.so")
 # math mode (tests/test_gpu_strict_parity.py).  ~2x slower.
 LIB_STRICT = os.path.join(_HERE, "libpick_ik_amd_strict.so")
 HEADERS = ["pik_kernels.hpp", "pik_math.hpp", "pik_host.hpp", "pik_solver.hpp", "pik_launch.hpp", "pik_exact.hpp",
-           "pik_host_solve.hpp"]
+           "pik_host_solve.hpp", "pik_path.hpp", "pik_path_ops.hpp"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pick_ik_amd.h")
 DOFS = tuple(range(1, 17))
 BUILD_DIR = os.path.join(_HERE, "_build")
@@ -87,6 +89,19 @@ def _exact_objects():
 
 def _is_exact_obj(o) -> bool:
     return os.sep + "exact" + os.sep in o[0]
+
+
+def _path_objects(flavour: str):
+    """the per-length objects of the waypoint-path kernels (pik_path_inst.hip -> pik_path.hpp) of one flavour: "fast",
+    "exact" or "strict".  Translation units of their own, linked behind everything else: the objects of pik_inst.hip are
+    compiled from the same text and linked in the same order with or without them.  The common-configuration
+    flavours have none (they return the general kernels' bits; pik_amd.hip path_ops_of routes their calls there)."""
+    d = os.path.join(BUILD_DIR, flavour)
+    fl = EXACT_FLAGS if flavour == "exact" else []
+    only = os.environ.get("PIK_ONLY_D")
+    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
+    return [(os.path.join(d, f"pik_path_inst_d{n}.o"), "pik_path_inst.hip",
+             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
 
 
 def _common_objects(goals: bool = False):
@@ -194,14 +209,15 @@ def _deps(src, strict_flags: bool):
 
 
 def _sources():
-    return ([os.path.join(CSRC, f) for f in ("pik_amd.hip", "pik_inst.hip", "pik_urdf.hpp", *HEADERS)] +
+    return ([os.path.join(CSRC, f) for f in ("pik_amd.hip", "pik_inst.hip", "pik_path_inst.hip", "pik_urdf.hpp", *HEADERS)] +
             [HEADER, os.path.abspath(__file__)])
 
 
 def _lib_stamp(strict: bool) -> str:
     """what a library was linked from: flavour flags + the chain lengths with real kernels"""
     flags = _flavor_flags(strict) + ([] if strict else ["+exact:"] + EXACT_FLAGS + ["+common:"] + COMMON_FLAGS + ["+common_goals:"] + COMMON_GOALS_FLAGS)
-    return _stamp(flags + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
+    # (+paths: the waypoint-path objects are linked in -- a library from before them is not this one)
+    return _stamp(flags + ["+paths", "only=" + os.environ.get("PIK_ONLY_D", "all")])
 
 
 def is_stale(lib: str = LIB) -> bool:
@@ -253,11 +269,28 @@ FLAVOUR_FLAGS = {
 _flavour_sha_cache = {}
 
 
+def _host_api_lines():
+    """the lines of the public header between its [host-api-begin] and [host-api-end] comments: declarations of host
+    entry points added after the committed kernel profiles were taken.  They are no device source -- flavour_sha leaves
+    them out, so that new host API does not mark the profiles of kernels nobody touched as stale (the header itself
+    declares them to every pass of every compiler)."""
+    out, inside = set(), False
+    for n, line in enumerate(open(HEADER).read().splitlines(), 1):
+        if "[host-api-begin]" in line:
+            inside = True
+        if inside:
+            out.add(n)
+        if "[host-api-end]" in line:
+            inside = False
+    return out
+
+
 def flavour_sha(namespace: str, dof: int = 7) -> str:
     """Hash of the DEVICE source of one kernel flavour: pik_inst.hip preprocessed with the flavour's flags
     (`hipcc -E`, device side), reduced to the lines that come from this repository's own files (csrc/, include/).
     Comments and the branches the flavour's macros switch off are not in it, so an edit of pik_exact.hpp or of a
-    PIK_STRICT block leaves the hash of the fast flavours alone.  The flags are part of the hash.  bench.py compares it
+    PIK_STRICT block leaves the hash of the fast flavours alone; neither are the header's host-only declarations
+    (_host_api_lines).  The flags are part of the hash.  bench.py compares it
     with the hash stored beside the PMC counters of a flavour (profiles/roofline_inputs.json: roofline.inputs_stale)."""
     key = (namespace, dof)
     if key in _flavour_sha_cache:
@@ -269,17 +302,21 @@ def flavour_sha(namespace: str, dof: int = 7) -> str:
     if r.returncode != 0:
         raise RuntimeError(f"{' '.join(cmd)}\n{r.stderr[-2000:]}")
     own = (os.path.realpath(CSRC) + os.sep, os.path.realpath(HEADER))
+    host_api = _host_api_lines()
     h = hashlib.sha256(" ".join(flags).encode())
-    keep = False
+    keep, in_header, lineno = False, False, 0
     for line in r.stdout.splitlines():
         if line.startswith("# ") and '"' in line:  # line marker: # <n> "<file>" <flags>
             f = line.split('"')[1]
             rp = os.path.realpath(f if os.path.isabs(f) else os.path.join(CSRC, f))
             keep = rp.startswith(own[0]) or rp == own[1]
+            in_header = rp == own[1]
+            lineno = int(line.split()[1])  # (the line the NEXT output line comes from)
             continue
-        if keep and line.strip():
+        if keep and line.strip() and not (in_header and lineno in host_api):
             h.update(line.strip().encode())
             h.update(b"\n")
+        lineno += 1
     _flavour_sha_cache[key] = h.hexdigest()[:16]
     return _flavour_sha_cache[key]
 
@@ -292,9 +329,10 @@ def ledger_rows():
     compiler's resource remarks kept beside the objects; None when an object has none (not built here)"""
     from . import kernel_resources as KR
     rows = []
-    for o in _objects(False) + _exact_objects() + _common_objects() + _common_objects(True) + _objects(True):
+    for o in (_objects(False) + _exact_objects() + _common_objects() + _common_objects(True) + _objects(True) +
+              _path_objects("fast") + _path_objects("exact") + _path_objects("strict")):
         res = o[0] + ".res"
-        if o[1] != "pik_inst.hip":
+        if o[1] not in ("pik_inst.hip", "pik_path_inst.hip"):
             continue
         if not os.path.exists(res):
             return None
@@ -341,6 +379,8 @@ def build_library(force: bool = False, verbose: bool = False, strict_too: bool =
         objs = _objects(strict)
         if not strict:  # + the exact kernels + the common-configuration kernels
             objs = objs + _exact_objects() + _common_objects() + _common_objects(True)
+        # + the waypoint-path kernels, behind everything that was there before them
+        objs = objs + (_path_objects("strict") if strict else _path_objects("fast") + _path_objects("exact"))
         stale = [o for o in objs if force or _obj_stale(*o, _is_strict_obj(o))]
         jobs += [(o, _is_strict_obj(o)) for o in stale if (o, _is_strict_obj(o)) not in jobs]
         relink.append((lib, [o[0] for o in objs]))

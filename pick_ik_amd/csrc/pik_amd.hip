@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "pik_path_ops.hpp"
 #include "pik_solver.hpp"
 #include "pik_urdf.hpp"
 
@@ -44,6 +45,14 @@ PIK_LITERAL_OPS(1) PIK_LITERAL_OPS(2) PIK_LITERAL_OPS(3) PIK_LITERAL_OPS(4) PIK_
 PIK_LITERAL_OPS(7) PIK_LITERAL_OPS(8) PIK_LITERAL_OPS(9) PIK_LITERAL_OPS(10) PIK_LITERAL_OPS(11) PIK_LITERAL_OPS(12)
 PIK_LITERAL_OPS(13) PIK_LITERAL_OPS(14) PIK_LITERAL_OPS(15) PIK_LITERAL_OPS(16)
 #undef PIK_LITERAL_OPS
+// (the waypoint-path kernels, pik_path_inst.hip: built for this flavour and the general one -- the kernels of the
+//  common configuration return the general ones' bits, a path call of theirs is served by the general ones)
+#define PIK_LITERAL_PATH_OPS(N) const void* path_ops_d##N();
+PIK_LITERAL_PATH_OPS(1) PIK_LITERAL_PATH_OPS(2) PIK_LITERAL_PATH_OPS(3) PIK_LITERAL_PATH_OPS(4)
+PIK_LITERAL_PATH_OPS(5) PIK_LITERAL_PATH_OPS(6) PIK_LITERAL_PATH_OPS(7) PIK_LITERAL_PATH_OPS(8)
+PIK_LITERAL_PATH_OPS(9) PIK_LITERAL_PATH_OPS(10) PIK_LITERAL_PATH_OPS(11) PIK_LITERAL_PATH_OPS(12)
+PIK_LITERAL_PATH_OPS(13) PIK_LITERAL_PATH_OPS(14) PIK_LITERAL_PATH_OPS(15) PIK_LITERAL_PATH_OPS(16)
+#undef PIK_LITERAL_PATH_OPS
 } // namespace pik_exact
 // ... and the kernels specialised for the common configuration (flavour -DPIK_COMMON=1, namespace pik_common;
 // pik_math.hpp says what that is and what it buys)
@@ -162,6 +171,28 @@ const pik::LaunchOps* solve_ops_of(const pikamd_solver* s, const pikamd_params* 
 
 int no_kernels(int dof) {
     return fail(PIKAMD_EUNSUPPORTED, "dof %d: kernels are instantiated for 1..16", dof);
+}
+
+// the waypoint-path kernels of a call: the flavour ops_of picks (a call with the common configuration: the general one)
+const pik::PathOps* path_ops_of(const pikamd_solver* s, const pikamd_params* p) {
+#if !defined(PIK_STRICT)
+    if (needs_literal(s, p)) {
+        const void* o = nullptr;
+        switch (s->chain.dof) {
+#define PIK_LITERAL_PATH_CASE(N) case N: o = pik_exact::path_ops_d##N(); break;
+            PIK_LITERAL_PATH_CASE(1) PIK_LITERAL_PATH_CASE(2) PIK_LITERAL_PATH_CASE(3) PIK_LITERAL_PATH_CASE(4)
+            PIK_LITERAL_PATH_CASE(5) PIK_LITERAL_PATH_CASE(6) PIK_LITERAL_PATH_CASE(7) PIK_LITERAL_PATH_CASE(8)
+            PIK_LITERAL_PATH_CASE(9) PIK_LITERAL_PATH_CASE(10) PIK_LITERAL_PATH_CASE(11) PIK_LITERAL_PATH_CASE(12)
+            PIK_LITERAL_PATH_CASE(13) PIK_LITERAL_PATH_CASE(14) PIK_LITERAL_PATH_CASE(15) PIK_LITERAL_PATH_CASE(16)
+#undef PIK_LITERAL_PATH_CASE
+            default: break;
+        }
+        return static_cast<const pik::PathOps*>(o);
+    }
+#else
+    (void)p;
+#endif
+    return pik::path_ops(s->chain.dof);
 }
 
 size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
@@ -1225,6 +1256,133 @@ const char* pikamd_kernel_name(const pikamd_solver* s, const pikamd_params* p) {
 #endif
     snprintf(m->kernel_name, sizeof m->kernel_name, "%s::%s<%d>", ns,
              p->mode == 1 ? "ik_gradient_kernel" : "memetic_kernel", s->chain.dof);
+    return m->kernel_name;
+}
+
+} // extern "C"
+
+// ---- Cartesian waypoint paths (pik_path.hpp) ----------------------------------------------------
+namespace {
+
+// what both path entry points refuse; `any_null`: some required array is NULL
+int check_paths(const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, bool any_null, pik::ParamsK& pk) {
+    if (int rc = check_solver(s)) return rc;
+    if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
+    if (p->mode != 1)
+        return fail(PIKAMD_EINVAL, "pikamd_solve_paths: waypoint paths are solved in local mode (mode = 1), got mode %d",
+                    (int)p->mode);
+    if (W < 1 || P < 0)
+        return fail(PIKAMD_EINVAL, "pikamd_solve_paths: %lld paths of %d waypoints: expected P >= 0 and W >= 1",
+                    (long long)P, (int)W);
+    if (s->opt.soa)
+        return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_solve_paths (its arrays are [P][W][dof])");
+    if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
+    if (P > 0 && any_null)
+        return fail(PIKAMD_EINVAL, "pikamd_solve_paths: goal_pos_quat, start, solution and status must not be NULL");
+    return 0;
+}
+
+// the flavour that serves a path call of this handle, and whether it is an exact one
+const char* path_flavour(const pikamd_solver* s, const pikamd_params* p, bool* exact) {
+#if defined(PIK_STRICT)
+    (void)s;
+    (void)p;
+    *exact = true;
+    return "pik_strict";
+#else
+    *exact = needs_literal(s, p);
+    return *exact ? "pik_exact" : "pik";
+#endif
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_solve_paths_device(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                  const double* d_goal_pos_quat, const double* d_start, const double* d_max_joint_step,
+                                  double* d_solution, int32_t* d_status, double* d_final_cost, pikamd_stats* d_stats,
+                                  int32_t* d_reached, void* stream, int32_t slot) {
+    pik::ParamsK pk;
+    if (int rc = check_paths(s, p, P, W, !d_goal_pos_quat || !d_start || !d_solution || !d_status, pk)) return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (P == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    const pik::PathOps* ops = path_ops_of(s, p);
+    if (!ops) return no_kernels(s->chain.dof);
+    HIP_TRY(hipSetDevice(s->device));
+    const pik::PathArgs a = {P, W, 0, d_goal_pos_quat, d_start, d_max_joint_step, d_solution, d_status,
+                             d_final_cost, d_stats, d_reached};
+    return ops->solve(s, pk, a, (hipStream_t)stream, slot);
+}
+
+int32_t pikamd_solve_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, const double* goal_pos_quat,
+                           const double* start, const double* max_joint_step, double* solution, int32_t* status,
+                           double* final_cost, pikamd_stats* stats, int32_t* reached) {
+    pik::ParamsK pk;
+    if (int rc = check_paths(s, p, P, W, !goal_pos_quat || !start || !solution || !status, pk)) return rc;
+    if (P == 0) return 0;
+    if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
+    const pik::PathOps* ops = path_ops_of(s, p);
+    if (!ops) return no_kernels(s->chain.dof);
+    // staged like pikamd_solve_batch, through the synchronous entry points' job: one copy in, the kernel, one copy out
+    const int job = PIKAMD_MAX_HOST_JOBS - 1;
+    pik::HostJob& J = s->jobs[job];
+    if (J.pending) return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", job);
+    HIP_TRY(hipSetDevice(s->device));
+    if (!J.stream) HIP_TRY(hipStreamCreateWithFlags(&J.stream, hipStreamNonBlocking));
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, rows = (size_t)P * (size_t)W;
+    const size_t off_goal = 0, off_start = off_goal + sizeof(double) * g7 * rows;
+    const size_t off_step = off_start + sizeof(double) * d * (size_t)P;
+    const size_t in_bytes = off_step + (max_joint_step ? sizeof(double) * d : 0);
+    const size_t off_solution = in_bytes, off_cost = off_solution + sizeof(double) * d * rows;
+    const size_t off_stats = off_cost + sizeof(double) * rows, off_status = off_stats + sizeof(pikamd_stats) * rows;
+    const size_t off_reached = off_status + align8(sizeof(int32_t) * rows);
+    const size_t total = off_reached + align8(sizeof(int32_t) * (size_t)P);
+    if (int rc = J.dev.ensure(total)) return rc;
+    if (int rc = J.host.ensure(total)) return rc;
+    char* hb = (char*)J.host.p;
+    char* db = (char*)J.dev.p;
+    std::memcpy(hb + off_goal, goal_pos_quat, sizeof(double) * g7 * rows);
+    std::memcpy(hb + off_start, start, sizeof(double) * d * (size_t)P);
+    if (max_joint_step) std::memcpy(hb + off_step, max_joint_step, sizeof(double) * d);
+    HIP_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, J.stream));
+    const pik::PathArgs a = {P, W, 0, (const double*)(db + off_goal), (const double*)(db + off_start),
+                             max_joint_step ? (const double*)(db + off_step) : nullptr, (double*)(db + off_solution),
+                             (int*)(db + off_status), (double*)(db + off_cost), (void*)(db + off_stats),
+                             (int*)(db + off_reached)};
+    // (work of this call may be in flight from here on: the stream is drained before an error is returned)
+    if (int rc = ops->solve(s, pk, a, J.stream, pik::N_DEVICE_SLOTS + job)) {
+        (void)hipStreamSynchronize(J.stream);
+        return rc;
+    }
+    {
+        hipError_t e = hipMemcpyAsync(hb + in_bytes, db + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, J.stream);
+        const hipError_t e2 = hipStreamSynchronize(J.stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(PIKAMD_EHIP, "pikamd_solve_paths: %s (its results are lost)", hipGetErrorString(e));
+    }
+    std::memcpy(solution, hb + off_solution, sizeof(double) * d * rows);
+    std::memcpy(status, hb + off_status, sizeof(int32_t) * rows);
+    if (final_cost) std::memcpy(final_cost, hb + off_cost, sizeof(double) * rows);
+    if (stats) std::memcpy(stats, hb + off_stats, sizeof(pikamd_stats) * rows);
+    if (reached) std::memcpy(reached, hb + off_reached, sizeof(int32_t) * (size_t)P);
+    return 0;
+}
+
+const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
+    if (!s || !p) return "";
+    pikamd_solver* m = const_cast<pikamd_solver*>(s);
+    bool exact = false;
+    const char* ns = path_flavour(s, p, &exact);
+    const int lanes = pik::path_lanes(s, P, exact), dof = s->chain.dof;
+    if (lanes == 1)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_kernel<%d,%s>", ns, dof, s->n_tips > 1 ? "true" : "false");
+    else if (exact)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_team_kernel<%d,%d>", ns, dof, lanes);
+    else
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_wide_kernel<%d,%d,%s>", ns, dof, lanes,
+                 s->n_tips > 1 ? "true" : "false");
     return m->kernel_name;
 }
 

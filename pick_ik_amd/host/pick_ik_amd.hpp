@@ -147,6 +147,16 @@ struct BatchResult {
     std::vector<pikamd_stats> stats;
 };
 
+// Solver::ik_gradient_paths: P paths of W waypoints, row-major [P][W]
+struct PathResult {
+    std::vector<double> solution; // [P][W][dof]: the answer of a held waypoint, else the path's last held configuration
+    std::vector<int32_t> status;  // [P][W]: PIKAMD_SUCCESS / PIKAMD_APPROXIMATE, the failure a path stopped at
+                                  // (PIKAMD_NO_IK_SOLUTION / PIKAMD_PATH_JUMP), PIKAMD_NOT_ATTEMPTED behind it
+    std::vector<double> cost;     // [P][W]
+    std::vector<pikamd_stats> stats;
+    std::vector<int32_t> reached; // [P] leading held waypoints: reached / W is computeCartesianPath's fraction
+};
+
 inline int32_t joint_type_of(const Joint& J) {
     if (J.planar >= 1 && J.planar <= 3) return PIKAMD_JOINT_PLANAR_X + (J.planar - 1);
     if (J.floating >= 1 && J.floating <= 7) return PIKAMD_JOINT_FLOATING_TX + (J.floating - 1);
@@ -392,6 +402,41 @@ class Solver {
                                   bool approx_solution = false,
                                   const std::vector<double>* ik_seed_states = nullptr) const {
         return batch(to_params(costs, nullptr, &params, approx_solution), seeds, goals, 0, 0, ik_seed_states);
+    }
+
+    // Cartesian waypoint paths (pikamd_solve_paths): goals [P][W] ([P][W][n_tips] for several tips) row-major,
+    // start [P][dof]; every waypoint is solved by ik_gradient from the previous waypoint's answer (the start of the
+    // search and the minimal-displacement reference), a path stops at its first failure.  max_joint_step [dof]
+    // (optional): a waypoint that moves a variable further than its entry is refused (PIKAMD_PATH_JUMP); an entry
+    // <= 0 sets no limit.  One kernel launch for the whole call.
+    PathResult ik_gradient_paths(const std::vector<double>& start, const std::vector<Pose>& goals, int waypoints,
+                                 const CostSpec& costs, const GradientIkParams& params, bool approx_solution = false,
+                                 const std::vector<double>* max_joint_step = nullptr) const {
+        if (waypoints < 1) throw std::invalid_argument("pick_ik_amd: a path has at least one waypoint");
+        const size_t per_path = static_cast<size_t>(waypoints) * static_cast<size_t>(n_tips_);
+        if (goals.size() % per_path != 0) throw std::invalid_argument("pick_ik_amd: goals size is not a multiple of waypoints * n_tips");
+        const size_t P = goals.size() / per_path, rows = P * static_cast<size_t>(waypoints);
+        if (start.size() != P * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: start size != P * dof");
+        if (max_joint_step && static_cast<int>(max_joint_step->size()) != dof_)
+            throw std::invalid_argument("pick_ik_amd: max_joint_step size != dof");
+        const pikamd_params p = to_params(costs, nullptr, &params, approx_solution);
+        std::vector<double> g7(7 * goals.size());
+        for (size_t b = 0; b < goals.size(); ++b) {
+            const Pose& g = goals[b];
+            const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+            for (int k = 0; k < 7; ++k) g7[7 * b + k] = v[k];
+        }
+        PathResult r;
+        r.solution.resize(rows * dof_);
+        r.status.resize(rows);
+        r.cost.resize(rows);
+        r.stats.resize(rows);
+        r.reached.resize(P);
+        if (pikamd_solve_paths(h_, &p, static_cast<int64_t>(P), waypoints, g7.data(), start.data(),
+                               max_joint_step ? max_joint_step->data() : nullptr, r.solution.data(), r.status.data(),
+                               r.cost.data(), r.stats.data(), r.reached.data()) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return r;
     }
 
     pikamd_solver* handle() const { return h_; }

@@ -21,6 +21,8 @@ LIB_STRICT_PATH = os.environ.get("PIK_LIB_STRICT") or os.path.join(_HERE, "libpi
 SUCCESS = 1
 APPROXIMATE = 2
 NO_IK_SOLUTION = -31
+NOT_ATTEMPTED = 0  # solve_paths: a waypoint behind the one its path stopped at
+PATH_JUMP = -1001  # solve_paths: solved, but a variable moved further than max_joint_step allows
 MAX_SLOTS = 128
 MAX_BATCHES = 64
 MAX_HOST_JOBS = 16
@@ -162,6 +164,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_solve_batches_device", "pikamd_solve_batches_async", "pikamd_wait", "pikamd_solve_batches",
     "pikamd_urdf_extract", "pikamd_create_from_urdf", "pikamd_set_option", "pikamd_solve_batch_host", "pikamd_set_mimic_joints",
     "pikamd_shard_bounds", "pikamd_solve_batch_sharded", "pikamd_self_test", "pikamd_self_test_cost",
+    "pikamd_solve_paths", "pikamd_solve_paths_device", "pikamd_path_kernel_name",
 )
 
 _libs = {}
@@ -244,6 +247,13 @@ def lib(strict: bool = False):
     L.pikamd_version.restype = C.c_char_p
     L.pikamd_kernel_name.restype = C.c_char_p
     L.pikamd_kernel_name.argtypes = [vp, C.POINTER(Params)]
+    L.pikamd_solve_paths.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, dp, dp, dp, dp, ip, dp, vp, ip]
+    L.pikamd_solve_paths.restype = C.c_int32
+    L.pikamd_solve_paths_device.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            vp, C.c_int32]
+    L.pikamd_solve_paths_device.restype = C.c_int32
+    L.pikamd_path_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
+    L.pikamd_path_kernel_name.restype = C.c_char_p
     for name in ("pikamd_create", "pikamd_variables", "pikamd_fk_batch", "pikamd_cost_batch",
                  "pikamd_gd_step_batch", "pikamd_solve_batch", "pikamd_solve_batch_device",
                  "pikamd_fk_batch_device", "pikamd_solve_batches_device",
@@ -591,6 +601,57 @@ class Solver:
 
     def kernel_name(self, params: Params) -> str:
         return self._L.pikamd_kernel_name(self._h, C.byref(params)).decode()
+
+    # ---- Cartesian waypoint paths ---------------------------------------------------------
+    def solve_paths(self, params: Params, goals, start, max_joint_step=None):
+        """pikamd_solve_paths: P paths of W waypoints in local mode (params.mode = 1), every waypoint solved from the
+        previous waypoint's answer, a path stopping at its first failure -- one launch.  goals [P][W][7]
+        ([P][W][n_tips][7] for several tips), start [P][dof], max_joint_step [dof] or None (an entry <= 0: no limit for
+        that variable).  Returns (solution [P][W][dof], status [P][W], cost [P][W], stats [P][W], reached [P]); the
+        result is what the loop of solve_batch calls in include/pick_ik_amd.h returns, bit for bit."""
+        self._env_options()
+        goals = _f64(goals)
+        tail = (7,) if self.n_tips == 1 else (self.n_tips, 7)
+        if goals.ndim != 2 + len(tail) or goals.shape[2:] != tail:
+            raise ValueError(f"goals: expected [P][W]{list(tail)}, got {list(goals.shape)}")
+        P, W = goals.shape[:2]
+        if W < 1:
+            raise ValueError("goals: a path has at least one waypoint")
+        start = _f64(start)
+        if start.shape != (P, self.dof):
+            raise ValueError(f"start: expected [{P}][{self.dof}], got {list(start.shape)}")
+        step = None
+        if max_joint_step is not None:
+            step = _f64(max_joint_step)
+            if step.shape != (self.dof,):
+                raise ValueError(f"max_joint_step: expected [{self.dof}], got {list(step.shape)}")
+        sol = np.empty((P, W, self.dof))
+        status = np.empty((P, W), dtype=np.int32)
+        cost = np.empty((P, W))
+        stats = np.zeros((P, W), dtype=STATS_DTYPE)
+        reached = np.empty(P, dtype=np.int32)
+        self._chk(self._L.pikamd_solve_paths(self._h, C.byref(params), P, W, _dp(goals), _dp(start),
+                                             None if step is None else _dp(step), _dp(sol), _ip(status), _dp(cost),
+                                             stats.ctypes.data_as(C.c_void_p), _ip(reached)))
+        return sol, status, cost, stats, reached
+
+    def solve_paths_device(self, params: Params, P: int, W: int, d_goals: int, d_start: int, d_solution: int,
+                           d_status: int, d_max_joint_step: int = 0, d_cost: int = 0, d_stats: int = 0,
+                           d_reached: int = 0, stream: int = 0, slot: int = 0):
+        """Enqueue a path solve on HBM-resident buffers (raw device addresses); returns immediately -- the caller
+        synchronises the stream."""
+        self._env_options()
+        if P < 0 or W < 1:
+            raise ValueError(f"{P} paths of {W} waypoints: expected P >= 0 and W >= 1")
+        self._chk(self._L.pikamd_solve_paths_device(
+            self._h, C.byref(params), P, W, d_goals or None, d_start or None, d_max_joint_step or None,
+            d_solution or None, d_status or None, d_cost or None, d_stats or None, d_reached or None, stream or None,
+            slot))
+
+    def path_kernel_name(self, params: Params, P: int) -> str:
+        """the kernel solve_paths launches for P paths (pikamd_path_kernel_name)"""
+        self._env_options()
+        return self._L.pikamd_path_kernel_name(self._h, C.byref(params), P).decode()
 
 
 def shard_bounds(total: int, rank: int, world: int, strict: bool = False):
