@@ -489,6 +489,70 @@ int32_t pikamd_solve_paths_device(pikamd_solver* s, const pikamd_params* p, int6
 /* name of the kernel pikamd_solve_paths* launches for P paths (see pikamd_kernel_name), e.g.
  * `pik_exact::ik_path_team_kernel<7,16>` */
 const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
+
+/* ---- Local IK with random restarts ---------------------------------------------------------------
+ * The loop searchPositionIK runs around the solver (src/pick_ik_plugin.cpp:145-291): solve; when no solution came
+ * back, draw a random valid configuration (Robot::set_random_valid_configuration, src/robot.cpp:23-30, 87-95) and
+ * solve again from there -- for B problems and up to max_attempts attempts each in ONE launch.  p->mode must be 1
+ * (local mode).  The result is DEFINED as what this loop of pikamd_solve_batch calls returns, bit for bit:
+ *
+ *   init[b] = initial_guess ? initial_guess[b] : seed[b]
+ *   if some bounded variable j has !(init[b][j] <= qmax[j] && init[b][j] >= qmin[j]):   (src/pick_ik_plugin.cpp:152-159;
+ *       init[b] = draw(b, 0, init[b])                                                     a NaN is invalid)
+ *   for a in 0 .. max_attempts-1, for every b still open:
+ *     (sol, st, cost, stats) = pikamd_solve_batch(local mode, goal[b], seed = seed[b], initial_guess = init[b])
+ *     solution[b] = sol; status[b] = st; final_cost[b] = cost; stats[b] += stats (field by field); attempts[b] = a + 1
+ *     if st > 0: b is closed        (PIKAMD_SUCCESS or PIKAMD_APPROXIMATE: error_code SUCCESS ends the reference's loop)
+ *     else: init[b] = draw(b, a + 1, init[b])
+ *
+ *   draw(b, e, prev)[j] = bounded[j] ? (qmax[j] - qmin[j]) * u + qmin[j]
+ *                                    : ((prev[j] + pi) - (prev[j] - pi)) * u + (prev[j] - pi)
+ *     u = the [0,1) double of Philox stream RESTART (= 3), key (rng_seed, problem_offset + b), epoch e, individual 0,
+ *         slot j -- the counter / key layout of every other draw of this library (streams 1 and 2 are as they were).
+ *     Every product, sum and difference of draw is rounded on its own, in every kernel flavour: the restart states
+ *     are the same doubles whatever serves the call.  An unbounded variable's draw is centred on the PREVIOUS
+ *     attempt's start, as in the reference.
+ *
+ * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch.  With
+ * return_approximate_solution set, attempt 0 always closes a problem (attempts == 1 everywhere).  A batch cut into
+ * calls or shards with matching problem_offset gives the answers of one call.  The attempts of one problem are
+ * independent computations, so the library may run them one after the other or side by side (option
+ * search_schedule = adaptive | sequential | parallel: like the other scheduling options it changes no result).
+ * all_solution / all_status: when either is given EVERY attempt of every problem is run and recorded, without an
+ * early exit -- the rows behind a problem's winner are real results (several distinct IK solutions per target, for
+ * a caller who collision-checks them); row a is what one pikamd_solve_batch from start a returns.  The primary
+ * outputs are the loop's whether or not all_* is given.
+ * The approximate-solution gate (src/pick_ik_plugin.cpp:219-267) and the solution callback stay with the caller.
+ * GLOBAL mode (mode 0) is refused: a restart attempt of the memetic kernels would have to start a first pass from a
+ * device-side list of the failed problems, which their launch does not offer.
+ *   goal_pos_quat [B][n_tips][7], seed [B][dof], initial_guess [B][dof] (NULL = seed), solution [B][dof], status [B],
+ *   final_cost [B] (may be NULL), stats [B] (may be NULL), attempts [B] (may be NULL),
+ *   all_solution [B][max_attempts][dof] (may be NULL), all_status [B][max_attempts] (may be NULL).
+ * Not with the option joint_layout = soa.  B = 0 returns 0. */
+#define PIKAMD_MAX_ATTEMPTS 64
+/* host pointers; synchronous, staged through the library's own pinned buffers and stream like pikamd_solve_batch,
+ * behind the same automatic self test of the local-mode kernels */
+int32_t pikamd_search_batch(pikamd_solver* s, const pikamd_params* p, int64_t B, const double* goal_pos_quat,
+                            const double* seed, const double* initial_guess, uint64_t rng_seed,
+                            int64_t problem_offset, int32_t max_attempts, double* solution, int32_t* status,
+                            double* final_cost, pikamd_stats* stats, int32_t* attempts, double* all_solution,
+                            int32_t* all_status);
+/* device pointers; enqueues on `stream` and returns without synchronising, no self test (see
+ * pikamd_solve_batch_device for `slot`).  The per-attempt scratch of the parallel schedule belongs to the
+ * handle's slot; it grows only when a call needs more than any earlier call on that slot did (a grow frees, and a
+ * free synchronises the device: run the largest call first where that matters). */
+int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int64_t B,
+                                   const double* d_goal_pos_quat, const double* d_seed,
+                                   const double* d_initial_guess, uint64_t rng_seed, int64_t problem_offset,
+                                   int32_t max_attempts, double* d_solution, int32_t* d_status,
+                                   double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
+                                   double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot);
+/* name of the kernel pikamd_search_batch* launches for B problems of max_attempts attempts (see
+ * pikamd_kernel_name), e.g. `pik_exact::ik_search_team_kernel<7,16>`; *attempts_in_flight (may be NULL): 1 = the
+ * sequential schedule (a lane or team walks a problem's attempts), max_attempts = the parallel one (every attempt
+ * of every problem on the chip at once, a small finalize kernel behind them) */
+const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t B,
+                                      int32_t max_attempts, int32_t* attempts_in_flight);
 /* [host-api-end] */
 
 #ifdef __cplusplus

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pik_path_ops.hpp"
+#include "pik_search_ops.hpp"
 #include "pik_solver.hpp"
 #include "pik_urdf.hpp"
 
@@ -53,6 +54,13 @@ PIK_LITERAL_PATH_OPS(5) PIK_LITERAL_PATH_OPS(6) PIK_LITERAL_PATH_OPS(7) PIK_LITE
 PIK_LITERAL_PATH_OPS(9) PIK_LITERAL_PATH_OPS(10) PIK_LITERAL_PATH_OPS(11) PIK_LITERAL_PATH_OPS(12)
 PIK_LITERAL_PATH_OPS(13) PIK_LITERAL_PATH_OPS(14) PIK_LITERAL_PATH_OPS(15) PIK_LITERAL_PATH_OPS(16)
 #undef PIK_LITERAL_PATH_OPS
+// (... and the restart-search kernels, pik_search_inst.hip: likewise)
+#define PIK_LITERAL_SEARCH_OPS(N) const void* search_ops_d##N();
+PIK_LITERAL_SEARCH_OPS(1) PIK_LITERAL_SEARCH_OPS(2) PIK_LITERAL_SEARCH_OPS(3) PIK_LITERAL_SEARCH_OPS(4)
+PIK_LITERAL_SEARCH_OPS(5) PIK_LITERAL_SEARCH_OPS(6) PIK_LITERAL_SEARCH_OPS(7) PIK_LITERAL_SEARCH_OPS(8)
+PIK_LITERAL_SEARCH_OPS(9) PIK_LITERAL_SEARCH_OPS(10) PIK_LITERAL_SEARCH_OPS(11) PIK_LITERAL_SEARCH_OPS(12)
+PIK_LITERAL_SEARCH_OPS(13) PIK_LITERAL_SEARCH_OPS(14) PIK_LITERAL_SEARCH_OPS(15) PIK_LITERAL_SEARCH_OPS(16)
+#undef PIK_LITERAL_SEARCH_OPS
 } // namespace pik_exact
 // ... and the kernels specialised for the common configuration (flavour -DPIK_COMMON=1, namespace pik_common;
 // pik_math.hpp says what that is and what it buys)
@@ -76,6 +84,16 @@ PIK_COMMON_OPS(13) PIK_COMMON_OPS(14) PIK_COMMON_OPS(15) PIK_COMMON_OPS(16)
 #endif
 
 namespace {
+
+// What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
+// parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
+// kernels' translation units and stays as it is.
+struct SolverExt : pikamd_solver {
+    int search_schedule = pik::SEARCH_ADAPTIVE;
+    pik::DevBuf search_rows[pik::N_SLOTS];
+};
+SolverExt* ext_of(pikamd_solver* s) { return static_cast<SolverExt*>(s); }
+const SolverExt* ext_of(const pikamd_solver* s) { return static_cast<const SolverExt*>(s); }
 
 #if !defined(PIK_STRICT)
 const pik::LaunchOps* literal_ops(int dof) {
@@ -195,6 +213,28 @@ const pik::PathOps* path_ops_of(const pikamd_solver* s, const pikamd_params* p) 
     return pik::path_ops(s->chain.dof);
 }
 
+// ... and the restart-search kernels of a call, by the same rule
+const pik::SearchOps* search_ops_of(const pikamd_solver* s, const pikamd_params* p) {
+#if !defined(PIK_STRICT)
+    if (needs_literal(s, p)) {
+        const void* o = nullptr;
+        switch (s->chain.dof) {
+#define PIK_LITERAL_SEARCH_CASE(N) case N: o = pik_exact::search_ops_d##N(); break;
+            PIK_LITERAL_SEARCH_CASE(1) PIK_LITERAL_SEARCH_CASE(2) PIK_LITERAL_SEARCH_CASE(3) PIK_LITERAL_SEARCH_CASE(4)
+            PIK_LITERAL_SEARCH_CASE(5) PIK_LITERAL_SEARCH_CASE(6) PIK_LITERAL_SEARCH_CASE(7) PIK_LITERAL_SEARCH_CASE(8)
+            PIK_LITERAL_SEARCH_CASE(9) PIK_LITERAL_SEARCH_CASE(10) PIK_LITERAL_SEARCH_CASE(11) PIK_LITERAL_SEARCH_CASE(12)
+            PIK_LITERAL_SEARCH_CASE(13) PIK_LITERAL_SEARCH_CASE(14) PIK_LITERAL_SEARCH_CASE(15) PIK_LITERAL_SEARCH_CASE(16)
+#undef PIK_LITERAL_SEARCH_CASE
+            default: break;
+        }
+        return static_cast<const pik::SearchOps*>(o);
+    }
+#else
+    (void)p;
+#endif
+    return pik::search_ops(s->chain.dof);
+}
+
 size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 } // namespace
@@ -242,7 +282,7 @@ static int32_t create_solver(const pik::ChainHost* chains, int n_tips, int32_t d
     HIP_TRY(hipSetDevice(device_ordinal));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device_ordinal));
-    pikamd_solver* s = new (std::nothrow) pikamd_solver();
+    pikamd_solver* s = new (std::nothrow) SolverExt();
     if (!s) return fail(PIKAMD_EHIP, "out of host memory");
     s->device = device_ordinal;
     s->num_cu = prop.multiProcessorCount;
@@ -384,12 +424,13 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : s->stage) b.release();
     for (auto& b : s->slot_state) b.release();
     for (auto& b : s->slot_soa) b.release();
+    for (auto& b : ext_of(s)->search_rows) b.release();
     for (auto& j : s->jobs) {
         j.dev.release();
         j.host.release();
         if (j.stream) (void)hipStreamDestroy(j.stream);
     }
-    delete s;
+    delete ext_of(s);
 }
 
 int32_t pikamd_variables(const pikamd_solver* s, double* out) {
@@ -921,6 +962,13 @@ int32_t pikamd_set_option(pikamd_solver* s, const char* name, const char* value)
         (n == "host_max_time" ? o.host_max_time : o.host_gd_max_time) = x;
         return 0;
     }
+    if (n == "search_schedule") { // pikamd_search_batch*: a problem's attempts one after the other or side by side
+        int& sched = ext_of(s)->search_schedule;
+        if (v.empty() || v == "adaptive") { sched = pik::SEARCH_ADAPTIVE; return 0; }
+        if (v == "sequential") { sched = pik::SEARCH_SEQUENTIAL; return 0; }
+        if (v == "parallel") { sched = pik::SEARCH_PARALLEL; return 0; }
+        return fail(PIKAMD_EINVAL, "search_schedule: expected 'adaptive', 'sequential' or 'parallel', got '%s'", v.c_str());
+    }
     if (n == "regime") {
         if (v.empty() || v == "adaptive") { o.regime = 0; return 0; }
         if (v == "latency") { o.regime = 1; return 0; }
@@ -1382,6 +1430,191 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
         snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_team_kernel<%d,%d>", ns, dof, lanes);
     else
         snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_wide_kernel<%d,%d,%s>", ns, dof, lanes,
+                 s->n_tips > 1 ? "true" : "false");
+    return m->kernel_name;
+}
+
+} // extern "C"
+
+// ---- local IK with random restarts (pik_search.hpp) ----------------------------------------------
+namespace {
+
+// what both search entry points refuse; `any_null`: some required array is NULL
+int check_search(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t K, bool any_null, pik::ParamsK& pk) {
+    if (int rc = check_solver(s)) return rc;
+    if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
+    if (p->mode != 1)
+        return fail(PIKAMD_EINVAL,
+                    "pikamd_search_batch: restarts are served in local mode (mode = 1), got mode %d: a restart attempt of "
+                    "the memetic kernels would have to start a first pass from a device-side list of the failed problems, "
+                    "which their launch does not offer",
+                    (int)p->mode);
+    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
+        return fail(PIKAMD_EINVAL, "pikamd_search_batch: max_attempts %d: expected 1..%d", (int)K, PIKAMD_MAX_ATTEMPTS);
+    if (B < 0) return fail(PIKAMD_EINVAL, "pikamd_search_batch: B = %lld: expected B >= 0", (long long)B);
+    if (s->opt.soa)
+        return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_search_batch (its arrays are [B][dof])");
+    if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
+    if (B > 0 && any_null)
+        return fail(PIKAMD_EINVAL, "pikamd_search_batch: goal_pos_quat, seed, solution and status must not be NULL");
+    return 0;
+}
+
+pik::SearchPlan search_plan_of(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t K) {
+    bool exact = false;
+    (void)path_flavour(s, p, &exact);
+    return pik::search_plan(s, ext_of(s)->search_schedule, B, K, exact);
+}
+
+// Schedule, width and -- parallel schedule -- the per-attempt rows of a call: the caller's all_* arrays where given,
+// the slot's scratch for the rest.  The scratch grows only when a call needs more than any earlier one on the slot.
+int plan_search(pikamd_solver* s, const pikamd_params* p, int slot, pik::SearchArgs& a, double* all_solution,
+                int32_t* all_status) {
+    const pik::SearchPlan plan = search_plan_of(s, p, a.B, a.K);
+    a.parallel = plan.parallel ? 1 : 0;
+    a.lanes = plan.lanes;
+    a.every = (all_solution || all_status) ? 1 : 0;
+    a.row_solution = all_solution;
+    a.row_status = all_status;
+    a.row_cost = nullptr;
+    a.row_stats = nullptr;
+    if (!plan.parallel) return 0;
+    const size_t rows = (size_t)a.B * (size_t)a.K, d = (size_t)s->chain.dof;
+    const size_t off_stats = 0, off_cost = off_stats + sizeof(pikamd_stats) * rows;
+    const size_t off_solution = off_cost + sizeof(double) * rows;
+    const size_t off_status = off_solution + (all_solution ? 0 : sizeof(double) * d * rows);
+    const size_t total = off_status + (all_status ? 0 : align8(sizeof(int32_t) * rows));
+    pik::DevBuf& buf = ext_of(s)->search_rows[slot];
+    if (int rc = buf.ensure(total)) return rc;
+    char* w = (char*)buf.p;
+    a.row_stats = w + off_stats;
+    a.row_cost = (double*)(w + off_cost);
+    if (!all_solution) a.row_solution = (double*)(w + off_solution);
+    if (!all_status) a.row_status = (int*)(w + off_status);
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int64_t B, const double* d_goal_pos_quat,
+                                   const double* d_seed, const double* d_initial_guess, uint64_t rng_seed,
+                                   int64_t problem_offset, int32_t max_attempts, double* d_solution, int32_t* d_status,
+                                   double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
+                                   double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot) {
+    pik::ParamsK pk;
+    if (int rc = check_search(s, p, B, max_attempts, !d_goal_pos_quat || !d_seed || !d_solution || !d_status, pk)) return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (B == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    const pik::SearchOps* ops = search_ops_of(s, p);
+    if (!ops) return no_kernels(s->chain.dof);
+    HIP_TRY(hipSetDevice(s->device));
+    pik::SearchArgs a = {};
+    a.B = B;
+    a.K = max_attempts;
+    a.goal = d_goal_pos_quat;
+    a.seed = d_seed;
+    a.guess = d_initial_guess ? d_initial_guess : d_seed;
+    a.rng_seed = rng_seed;
+    a.problem_offset = problem_offset;
+    a.solution = d_solution;
+    a.status = d_status;
+    a.cost = d_final_cost;
+    a.stats = d_stats;
+    a.attempts = d_attempts;
+    if (int rc = plan_search(s, p, slot, a, d_all_solution, d_all_status)) return rc;
+    return ops->solve(s, pk, a, (hipStream_t)stream, slot);
+}
+
+int32_t pikamd_search_batch(pikamd_solver* s, const pikamd_params* p, int64_t B, const double* goal_pos_quat,
+                            const double* seed, const double* initial_guess, uint64_t rng_seed, int64_t problem_offset,
+                            int32_t max_attempts, double* solution, int32_t* status, double* final_cost,
+                            pikamd_stats* stats, int32_t* attempts, double* all_solution, int32_t* all_status) {
+    pik::ParamsK pk;
+    if (int rc = check_search(s, p, B, max_attempts, !goal_pos_quat || !seed || !solution || !status, pk)) return rc;
+    if (B == 0) return 0;
+    if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
+    const pik::SearchOps* ops = search_ops_of(s, p);
+    if (!ops) return no_kernels(s->chain.dof);
+    // staged like pikamd_solve_paths, through the synchronous entry points' job: one copy in, the kernels, one copy out
+    const int job = PIKAMD_MAX_HOST_JOBS - 1;
+    pik::HostJob& J = s->jobs[job];
+    if (J.pending) return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", job);
+    HIP_TRY(hipSetDevice(s->device));
+    if (!J.stream) HIP_TRY(hipStreamCreateWithFlags(&J.stream, hipStreamNonBlocking));
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, n = (size_t)B, rows = n * (size_t)max_attempts;
+    const size_t off_goal = 0, off_seed = off_goal + sizeof(double) * g7 * n, off_guess = off_seed + sizeof(double) * d * n;
+    const size_t in_bytes = off_guess + (initial_guess ? sizeof(double) * d * n : 0);
+    const size_t off_solution = in_bytes, off_cost = off_solution + sizeof(double) * d * n;
+    const size_t off_stats = off_cost + sizeof(double) * n, off_status = off_stats + sizeof(pikamd_stats) * n;
+    const size_t off_attempts = off_status + align8(sizeof(int32_t) * n);
+    const size_t off_all_solution = off_attempts + align8(sizeof(int32_t) * n);
+    const size_t off_all_status = off_all_solution + (all_solution ? sizeof(double) * d * rows : 0);
+    const size_t total = off_all_status + (all_status ? align8(sizeof(int32_t) * rows) : 0);
+    if (int rc = J.dev.ensure(total)) return rc;
+    if (int rc = J.host.ensure(total)) return rc;
+    char* hb = (char*)J.host.p;
+    char* db = (char*)J.dev.p;
+    pik::SearchArgs a = {};
+    a.B = B;
+    a.K = max_attempts;
+    a.goal = (const double*)(db + off_goal);
+    a.seed = (const double*)(db + off_seed);
+    a.guess = initial_guess ? (const double*)(db + off_guess) : a.seed;
+    a.rng_seed = rng_seed;
+    a.problem_offset = problem_offset;
+    a.solution = (double*)(db + off_solution);
+    a.status = (int*)(db + off_status);
+    a.cost = (double*)(db + off_cost);
+    a.stats = (void*)(db + off_stats);
+    a.attempts = (int*)(db + off_attempts);
+    const int slot = pik::N_DEVICE_SLOTS + job;
+    if (int rc = plan_search(s, p, slot, a, all_solution ? (double*)(db + off_all_solution) : nullptr,
+                             all_status ? (int32_t*)(db + off_all_status) : nullptr))
+        return rc;
+    std::memcpy(hb + off_goal, goal_pos_quat, sizeof(double) * g7 * n);
+    std::memcpy(hb + off_seed, seed, sizeof(double) * d * n);
+    if (initial_guess) std::memcpy(hb + off_guess, initial_guess, sizeof(double) * d * n);
+    HIP_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, J.stream));
+    // (work of this call may be in flight from here on: the stream is drained before an error is returned)
+    if (int rc = ops->solve(s, pk, a, J.stream, slot)) {
+        (void)hipStreamSynchronize(J.stream);
+        return rc;
+    }
+    {
+        hipError_t e = hipMemcpyAsync(hb + in_bytes, db + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, J.stream);
+        const hipError_t e2 = hipStreamSynchronize(J.stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(PIKAMD_EHIP, "pikamd_search_batch: %s (its results are lost)", hipGetErrorString(e));
+    }
+    std::memcpy(solution, hb + off_solution, sizeof(double) * d * n);
+    std::memcpy(status, hb + off_status, sizeof(int32_t) * n);
+    if (final_cost) std::memcpy(final_cost, hb + off_cost, sizeof(double) * n);
+    if (stats) std::memcpy(stats, hb + off_stats, sizeof(pikamd_stats) * n);
+    if (attempts) std::memcpy(attempts, hb + off_attempts, sizeof(int32_t) * n);
+    if (all_solution) std::memcpy(all_solution, hb + off_all_solution, sizeof(double) * d * rows);
+    if (all_status) std::memcpy(all_status, hb + off_all_status, sizeof(int32_t) * rows);
+    return 0;
+}
+
+const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t max_attempts,
+                                      int32_t* attempts_in_flight) {
+    if (attempts_in_flight) *attempts_in_flight = 0;
+    if (!s || !p || B < 0 || max_attempts < 1 || max_attempts > PIKAMD_MAX_ATTEMPTS) return "";
+    pikamd_solver* m = const_cast<pikamd_solver*>(s);
+    bool exact = false;
+    const char* ns = path_flavour(s, p, &exact);
+    const pik::SearchPlan plan = search_plan_of(s, p, B, max_attempts);
+    const int lanes = plan.lanes, dof = s->chain.dof;
+    if (attempts_in_flight) *attempts_in_flight = plan.parallel ? max_attempts : 1;
+    if (lanes == 1)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_kernel<%d,%s>", ns, dof, s->n_tips > 1 ? "true" : "false");
+    else if (exact)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_team_kernel<%d,%d>", ns, dof, lanes);
+    else
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_wide_kernel<%d,%d,%s>", ns, dof, lanes,
                  s->n_tips > 1 ? "true" : "false");
     return m->kernel_name;
 }

@@ -157,6 +157,14 @@ struct PathResult {
     std::vector<int32_t> reached; // [P] leading held waypoints: reached / W is computeCartesianPath's fraction
 };
 
+// Solver::ik_gradient_search_batch: local mode with random restarts
+struct SearchResult {
+    BatchResult batch;                 // what the loop of restarts returned per problem (stats summed over its attempts)
+    std::vector<int32_t> attempts;     // [B] attempts made: the winner's index + 1, max_attempts when none succeeded
+    std::vector<double> all_solution;  // [B][max_attempts][dof], only when every attempt was asked for
+    std::vector<int32_t> all_status;   // [B][max_attempts], likewise
+};
+
 inline int32_t joint_type_of(const Joint& J) {
     if (J.planar >= 1 && J.planar <= 3) return PIKAMD_JOINT_PLANAR_X + (J.planar - 1);
     if (J.floating >= 1 && J.floating <= 7) return PIKAMD_JOINT_FLOATING_TX + (J.floating - 1);
@@ -435,6 +443,51 @@ class Solver {
         if (pikamd_solve_paths(h_, &p, static_cast<int64_t>(P), waypoints, g7.data(), start.data(),
                                max_joint_step ? max_joint_step->data() : nullptr, r.solution.data(), r.status.data(),
                                r.cost.data(), r.stats.data(), r.reached.data()) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return r;
+    }
+
+    // Local mode with random restarts (pikamd_search_batch): what searchPositionIK's loop does around ik_gradient
+    // (src/pick_ik_plugin.cpp:145-291) for B problems in one launch -- solve from seeds[b] (or initial_guesses[b]); after
+    // a failure draw a random valid configuration keyed by (rng_seed, problem_offset + b, attempt) and solve again, up
+    // to max_attempts (1 .. PIKAMD_MAX_ATTEMPTS) times.  seeds [B][dof] stay the minimal-displacement reference and
+    // what a failure returns.  all_attempts: every attempt of every problem is run and recorded (several distinct
+    // solutions per target); the primary result is the loop's either way.
+    SearchResult ik_gradient_search_batch(const std::vector<double>& seeds, const std::vector<Pose>& goals,
+                                          const CostSpec& costs, const GradientIkParams& params, int max_attempts,
+                                          uint64_t rng_seed = 0, int64_t problem_offset = 0,
+                                          bool approx_solution = false, bool all_attempts = false,
+                                          const std::vector<double>* initial_guesses = nullptr) const {
+        if (max_attempts < 1 || max_attempts > PIKAMD_MAX_ATTEMPTS)
+            throw std::invalid_argument("pick_ik_amd: max_attempts outside 1 .. PIKAMD_MAX_ATTEMPTS");
+        if (goals.size() % static_cast<size_t>(n_tips_) != 0)
+            throw std::invalid_argument("pick_ik_amd: goals size is not a multiple of n_tips");
+        const size_t B = goals.size() / static_cast<size_t>(n_tips_), rows = B * static_cast<size_t>(max_attempts);
+        if (seeds.size() != B * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: seeds size != B * dof");
+        if (initial_guesses && initial_guesses->size() != seeds.size())
+            throw std::invalid_argument("pick_ik_amd: initial_guesses size != B * dof");
+        const pikamd_params p = to_params(costs, nullptr, &params, approx_solution);
+        std::vector<double> g7(7 * goals.size());
+        for (size_t b = 0; b < goals.size(); ++b) {
+            const Pose& g = goals[b];
+            const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+            for (int k = 0; k < 7; ++k) g7[7 * b + k] = v[k];
+        }
+        SearchResult r;
+        r.batch.solution.resize(B * dof_);
+        r.batch.status.resize(B);
+        r.batch.cost.resize(B);
+        r.batch.stats.resize(B);
+        r.attempts.resize(B);
+        if (all_attempts) {
+            r.all_solution.resize(rows * dof_);
+            r.all_status.resize(rows);
+        }
+        if (pikamd_search_batch(h_, &p, static_cast<int64_t>(B), g7.data(), seeds.data(),
+                                initial_guesses ? initial_guesses->data() : nullptr, rng_seed, problem_offset,
+                                max_attempts, r.batch.solution.data(), r.batch.status.data(), r.batch.cost.data(),
+                                r.batch.stats.data(), r.attempts.data(), all_attempts ? r.all_solution.data() : nullptr,
+                                all_attempts ? r.all_status.data() : nullptr) != 0)
             throw std::runtime_error(pikamd_last_error());
         return r;
     }

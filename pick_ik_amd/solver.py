@@ -23,6 +23,7 @@ APPROXIMATE = 2
 NO_IK_SOLUTION = -31
 NOT_ATTEMPTED = 0  # solve_paths: a waypoint behind the one its path stopped at
 PATH_JUMP = -1001  # solve_paths: solved, but a variable moved further than max_joint_step allows
+MAX_ATTEMPTS = 64  # search_batch: PIKAMD_MAX_ATTEMPTS
 MAX_SLOTS = 128
 MAX_BATCHES = 64
 MAX_HOST_JOBS = 16
@@ -165,6 +166,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_urdf_extract", "pikamd_create_from_urdf", "pikamd_set_option", "pikamd_solve_batch_host", "pikamd_set_mimic_joints",
     "pikamd_shard_bounds", "pikamd_solve_batch_sharded", "pikamd_self_test", "pikamd_self_test_cost",
     "pikamd_solve_paths", "pikamd_solve_paths_device", "pikamd_path_kernel_name",
+    "pikamd_search_batch", "pikamd_search_batch_device", "pikamd_search_kernel_name",
 )
 
 _libs = {}
@@ -254,6 +256,14 @@ def lib(strict: bool = False):
     L.pikamd_solve_paths_device.restype = C.c_int32
     L.pikamd_path_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
     L.pikamd_path_kernel_name.restype = C.c_char_p
+    L.pikamd_search_batch.argtypes = [vp, C.POINTER(Params), C.c_int64, dp, dp, dp, C.c_uint64, C.c_int64, C.c_int32,
+                                      dp, ip, dp, vp, ip, dp, ip]
+    L.pikamd_search_batch.restype = C.c_int32
+    L.pikamd_search_batch_device.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, C.c_uint64, C.c_int64,
+                                             C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32]
+    L.pikamd_search_batch_device.restype = C.c_int32
+    L.pikamd_search_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, ip]
+    L.pikamd_search_kernel_name.restype = C.c_char_p
     for name in ("pikamd_create", "pikamd_variables", "pikamd_fk_batch", "pikamd_cost_batch",
                  "pikamd_gd_step_batch", "pikamd_solve_batch", "pikamd_solve_batch_device",
                  "pikamd_fk_batch_device", "pikamd_solve_batches_device",
@@ -402,7 +412,7 @@ class Solver:
     # ---- scheduling options (pikamd_set_option) -------------------------------------------
     def set_option(self, name: str, value) -> None:
         """Pin one scheduling choice of this handle ("lanes_per_elite", "lanes_per_elite_schedule",
-        "passes", "two_per_simd", "regime"; None / "" restores the default).  Results never depend on
+        "passes", "two_per_simd", "regime", "search_schedule"; None / "" restores the default).  Results never depend on
         these."""
         v = b"" if value is None else str(value).encode()
         self._chk(self._L.pikamd_set_option(self._h, name.encode(), v))
@@ -652,6 +662,67 @@ class Solver:
         """the kernel solve_paths launches for P paths (pikamd_path_kernel_name)"""
         self._env_options()
         return self._L.pikamd_path_kernel_name(self._h, C.byref(params), P).decode()
+
+    # ---- local IK with random restarts ----------------------------------------------------
+    def search_batch(self, params: Params, goal_pos_quat, seed, max_attempts: int, rng_seed: int = 0,
+                     problem_offset: int = 0, initial_guess=None, all_attempts: bool = False):
+        """pikamd_search_batch: local mode (params.mode = 1) with up to max_attempts (1..MAX_ATTEMPTS) attempts per
+        problem, every attempt after a failure from a random valid configuration keyed by (rng_seed, problem_offset + b,
+        attempt) -- one launch.  Returns (solution [B][dof], status [B], cost [B], stats [B], attempts [B]) and, with
+        all_attempts, (all_solution [B][max_attempts][dof], all_status [B][max_attempts]) behind them: every attempt
+        of every problem, run without an early exit.  The result is what the loop of solve_batch calls in
+        include/pick_ik_amd.h returns, bit for bit."""
+        self._env_options()
+        goal = _f64(goal_pos_quat)
+        if goal.ndim < 2 or goal.size != goal.shape[0] * 7 * self.n_tips:
+            raise ValueError(f"goal_pos_quat: expected [B]{[7] if self.n_tips == 1 else [self.n_tips, 7]}, "
+                             f"got {list(goal.shape)}")
+        B = goal.shape[0]
+        seed = _f64(seed)
+        if seed.shape != (B, self.dof):
+            raise ValueError(f"seed: expected [{B}][{self.dof}], got {list(seed.shape)}")
+        guess = None
+        if initial_guess is not None:
+            guess = _f64(initial_guess)
+            if guess.shape != (B, self.dof):
+                raise ValueError(f"initial_guess: expected [{B}][{self.dof}], got {list(guess.shape)}")
+        K = int(max_attempts)
+        if not 1 <= K <= MAX_ATTEMPTS:
+            raise ValueError(f"max_attempts: expected 1..{MAX_ATTEMPTS}, got {max_attempts}")
+        sol = np.empty((B, self.dof))
+        status = np.empty(B, dtype=np.int32)
+        cost = np.empty(B)
+        stats = np.zeros(B, dtype=STATS_DTYPE)
+        attempts = np.empty(B, dtype=np.int32)
+        all_sol = np.empty((B, K, self.dof)) if all_attempts else None
+        all_st = np.empty((B, K), dtype=np.int32) if all_attempts else None
+        self._chk(self._L.pikamd_search_batch(
+            self._h, C.byref(params), B, _dp(goal), _dp(seed), None if guess is None else _dp(guess),
+            C.c_uint64(rng_seed), problem_offset, K, _dp(sol), _ip(status), _dp(cost), stats.ctypes.data_as(C.c_void_p),
+            _ip(attempts), None if all_sol is None else _dp(all_sol), None if all_st is None else _ip(all_st)))
+        if all_attempts:
+            return sol, status, cost, stats, attempts, all_sol, all_st
+        return sol, status, cost, stats, attempts
+
+    def search_batch_device(self, params: Params, B: int, d_goal: int, d_seed: int, max_attempts: int, d_solution: int,
+                            d_status: int, d_initial_guess: int = 0, d_cost: int = 0, d_stats: int = 0,
+                            d_attempts: int = 0, d_all_solution: int = 0, d_all_status: int = 0, rng_seed: int = 0,
+                            problem_offset: int = 0, stream: int = 0, slot: int = 0):
+        """Enqueue a restart search on HBM-resident buffers (raw device addresses); returns immediately -- the caller
+        synchronises the stream."""
+        self._env_options()
+        self._chk(self._L.pikamd_search_batch_device(
+            self._h, C.byref(params), B, d_goal or None, d_seed or None, d_initial_guess or None, C.c_uint64(rng_seed),
+            problem_offset, max_attempts, d_solution or None, d_status or None, d_cost or None, d_stats or None,
+            d_attempts or None, d_all_solution or None, d_all_status or None, stream or None, slot))
+
+    def search_kernel_name(self, params: Params, B: int, max_attempts: int):
+        """(the kernel search_batch launches for B problems of max_attempts attempts, attempts in flight per problem:
+        1 = the sequential schedule, max_attempts = the parallel one) -- pikamd_search_kernel_name"""
+        self._env_options()
+        n = C.c_int32(0)
+        name = self._L.pikamd_search_kernel_name(self._h, C.byref(params), B, max_attempts, C.byref(n)).decode()
+        return name, int(n.value)
 
 
 def shard_bounds(total: int, rank: int, world: int, strict: bool = False):
