@@ -8,14 +8,23 @@ kernels and the oracle share (a sine, an arctangent, a quaternion extraction) sh
   fk(chain, q)                        URDF origins (R = Rz(yaw) Ry(pitch) Rx(roll)), a Rodrigues rotation about the
                                       normalised axis for revolute / continuous joints, a translation along it for
                                       prismatic joints, planar joints as x / y translations + a rotation about z
-                                      (MoveIt's PlanarJointModel); the exact position and rotation matrix per tip
+                                      (MoveIt's PlanarJointModel); a floating joint (seven variables, one step) as
+                                      Translation(v0 v1 v2) * toRotationMatrix(w = v6, v3, v4, v5), the quaternion
+                                      NOT normalised (src/forward_kinematics.cpp:64-70): s^2 R' + (1 - s^2) I for a
+                                      quaternion of norm s, no rotation unless s = 1; a mimic joint (`chain.mimic`) as
+                                      one more step behind the joint of its `after_variable`, at multiplier *
+                                      q[master] + offset evaluated exactly; the exact position and matrix per tip
+  frame_quat(R, branch=None)          Eigen's matrix-to-quaternion conversion followed literally on ANY 3x3 matrix
+                                      (the trace branch when the trace is > 0, else the largest diagonal entry, the
+                                      later index only when strictly larger): the quaternion and the branch taken; for
+                                      a matrix that is no rotation the branches give different quaternions, so the
+                                      branch is part of the result.  `branch`: evaluate under that branch instead
+  branch_decisions(R)                 the comparisons the conversion made: their margins (|trace|, the differences of
+                                      the diagonal entries compared) and the branch the other outcome leads to
   angular_distance(R, goal_quat)      Eigen's angularDistance, 2 atan2(|vec|, |w|) of the relative quaternion
   cost(chain, params, goal, seed, q)  the upstream make_cost_fn (pose cost src/goal.cpp:51-78, joint goals :91-144,
                                       weight^2 composition :163-203) and the solution test (frame tests
                                       src/goal.cpp:27-36, joint goals against cost_threshold^2)
-
-Floating and mimic joints are not modelled: chains with them stay with the oracle (oracle/pik_oracle.c), whose
-literal chain product the exact flavours match bit for bit.
 
   step(chain, params, goal, seed, q)  step() of src/ik_gradient.cpp:24-94 taken literally, every cost by `cost`: the
                                       raw and normalised gradient, the line search and the clamped update (`Step`)
@@ -81,19 +90,48 @@ class _Path:
     axis: np.ndarray
     joint_type: np.ndarray
     tip_xyz_rpy: np.ndarray
+    mimic: tuple = ()  # the chain's MimicJoints of this path, in the order given
+
+
+def _check_path(p):
+    """the seven variables of a floating joint are consecutive and in MoveIt's order; a mimic joint follows a joint of
+    the path (or stands in front of the first) and is revolute or prismatic"""
+    n, j = len(p.variable), 0
+    inside = set()  # variables of a floating joint but its last: the joint acts at the seventh
+    while j < n:
+        jt = int(p.joint_type[j])
+        if jt in robots.FLOATING:
+            block = tuple(int(t) for t in p.joint_type[j:j + 7])
+            if block != tuple(robots.FLOATING):
+                raise ValueError(f"floating joint: variables {j}.. are {block}, not the seven of one joint in order")
+            inside.update(int(v) for v in p.variable[j:j + 6])
+            j += 7
+        else:
+            j += 1
+    on_path = set(int(v) for v in p.variable)
+    for m in p.mimic:
+        if int(m.joint_type) not in (robots.REVOLUTE, robots.PRISMATIC):
+            raise ValueError("mimic joint: neither revolute nor prismatic")
+        if m.after_variable != -1 and int(m.after_variable) not in on_path:
+            raise ValueError(f"mimic joint: variable {m.after_variable} moves no joint of its path")
+        if int(m.after_variable) in inside:
+            raise NotImplementedError("mimic joint inside the seven variables of a floating joint")
 
 
 def paths(chain):
     """the serial paths of a chain (one per tip frame)"""
-    if getattr(chain, "mimic", ()):
-        raise NotImplementedError("mimic joints: compare with the oracle")
+    mimic = tuple(getattr(chain, "mimic", ()))
     if hasattr(chain, "tips"):
-        ps = [_Path(t.variable, t.origin_xyz_rpy, t.axis, t.joint_type, t.tip_xyz_rpy) for t in chain.tips]
+        ps = [_Path(t.variable, t.origin_xyz_rpy, t.axis, t.joint_type, t.tip_xyz_rpy,
+                    tuple(m for m in mimic if int(m.tip) == k)) for k, t in enumerate(chain.tips)]
+        if any(not 0 <= int(m.tip) < len(ps) for m in mimic):
+            raise ValueError("mimic joint: no such tip")
     else:
-        ps = [_Path(np.arange(chain.dof), chain.origin_xyz_rpy, chain.axis, chain.joint_type, chain.tip_xyz_rpy)]
+        if any(int(m.tip) != 0 for m in mimic):
+            raise ValueError("mimic joint: no such tip")
+        ps = [_Path(np.arange(chain.dof), chain.origin_xyz_rpy, chain.axis, chain.joint_type, chain.tip_xyz_rpy, mimic)]
     for p in ps:
-        if any(int(t) in robots.FLOATING for t in p.joint_type):
-            raise NotImplementedError("floating joints: compare with the oracle")
+        _check_path(p)
     return ps
 
 
@@ -101,33 +139,69 @@ def _origin(xyz_rpy):
     return rpy_matrix(*(mpf(v) for v in xyz_rpy[3:])), [mpf(v) for v in xyz_rpy[:3]]
 
 
+def quat_matrix(w, x, y, z):
+    """Eigen's toRotationMatrix, which does not normalise: s^2 R' + (1 - s^2) I for a quaternion of norm s"""
+    return [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+            [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+            [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+
+
+def _unit_axis(axis):
+    a = [mpf(x) for x in axis]
+    nn = M.sqrt(a[0] ** 2 + a[1] ** 2 + a[2] ** 2)
+    return [x / nn for x in a]
+
+
+def mimic_value(m, q):
+    """multiplier * q[master] + offset, exact"""
+    return mpf(m.multiplier) * mpf(q[int(m.master_variable)]) + mpf(m.offset)
+
+
 def _fk_path(p, q):
     R, t = _ident(), [M.mpf(0)] * 3
-    for j in range(len(p.variable)):
-        jt = int(p.joint_type[j])
-        v = mpf(q[int(p.variable[j])])
-        if jt in (robots.PLANAR_X, robots.PLANAR_Y, robots.PLANAR_THETA):
-            k = jt - robots.PLANAR_X  # x, y: translations along the joint frame's x / y; theta: about z
-            if k == 0:
-                Ro, to = _origin(p.origin_xyz_rpy[j])
-                t = [a + b for a, b in zip(t, _matvec(R, to))]
-                R = _matmul(R, Ro)
-            n = [M.mpf(int(i == k)) for i in range(3)] if k < 2 else [M.mpf(0), M.mpf(0), M.mpf(1)]
-            jt = robots.REVOLUTE if k == 2 else robots.PRISMATIC
-        else:
-            Ro, to = _origin(p.origin_xyz_rpy[j])
-            t = [a + b for a, b in zip(t, _matvec(R, to))]
-            R = _matmul(R, Ro)
-            a = [mpf(x) for x in p.axis[j]]
-            nn = M.sqrt(a[0] ** 2 + a[1] ** 2 + a[2] ** 2)
-            n = [x / nn for x in a]
+
+    def place(xyz_rpy):
+        nonlocal R, t
+        Ro, to = _origin(xyz_rpy)
+        t = [a + b for a, b in zip(t, _matvec(R, to))]
+        R = _matmul(R, Ro)
+
+    def move(jt, n, v):
+        nonlocal R, t
         if jt == robots.PRISMATIC:
             t = [a + b for a, b in zip(t, _matvec(R, [x * v for x in n]))]
         else:
             R = _matmul(R, rodrigues(n, v))
-    Ro, to = _origin(p.tip_xyz_rpy)
-    t = [a + b for a, b in zip(t, _matvec(R, to))]
-    return t, _matmul(R, Ro)
+
+    def mimics(after):
+        for m in p.mimic:
+            if int(m.after_variable) == after:
+                place(m.origin_xyz_rpy)
+                move(int(m.joint_type), _unit_axis(m.axis), mimic_value(m, q))
+
+    mimics(-1)
+    j = 0
+    while j < len(p.variable):
+        jt = int(p.joint_type[j])
+        if jt == robots.FLOATING_TX:  # one step: the origin, the translation, the unnormalised quaternion's matrix
+            v = [mpf(q[int(p.variable[j + i])]) for i in range(7)]
+            place(p.origin_xyz_rpy[j])
+            t = [a + b for a, b in zip(t, _matvec(R, v[:3]))]
+            R = _matmul(R, quat_matrix(v[6], v[3], v[4], v[5]))
+            j += 6
+        elif jt in (robots.PLANAR_X, robots.PLANAR_Y, robots.PLANAR_THETA):
+            k = jt - robots.PLANAR_X  # x, y: translations along the joint frame's x / y; theta: about z
+            if k == 0:
+                place(p.origin_xyz_rpy[j])
+            n = [M.mpf(int(i == k)) for i in range(3)] if k < 2 else [M.mpf(0), M.mpf(0), M.mpf(1)]
+            move(robots.REVOLUTE if k == 2 else robots.PRISMATIC, n, mpf(q[int(p.variable[j])]))
+        else:
+            place(p.origin_xyz_rpy[j])
+            move(jt, _unit_axis(p.axis[j]), mpf(q[int(p.variable[j])]))
+        mimics(int(p.variable[j]))
+        j += 1
+    place(p.tip_xyz_rpy)
+    return t, R
 
 
 def fk(chain, q):
@@ -136,7 +210,9 @@ def fk(chain, q):
 
 
 def matrix_to_quat(R):
-    """the unit quaternion (w, x, y, z) of an exact rotation matrix, w >= 0"""
+    """the unit quaternion (w, x, y, z) of an EXACT rotation matrix, w >= 0, by the largest of the four candidates
+    (for a rotation every branch gives the same quaternion up to sign: `frame_quat` is the conversion the tip frame
+    takes, on any matrix)"""
     tr = R[0][0] + R[1][1] + R[2][2]
     cands = [tr, R[0][0], R[1][1], R[2][2]]
     k = max(range(4), key=lambda i: cands[i])
@@ -153,6 +229,57 @@ def matrix_to_quat(R):
         s = M.sqrt(1 + R[2][2] - R[0][0] - R[1][1]) * 2
         q = [(R[1][0] - R[0][1]) / s, (R[0][2] + R[2][0]) / s, (R[1][2] + R[2][1]) / s, s / 4]
     return [-x for x in q] if q[0] < 0 else q
+
+
+BRANCHES = ("w", "x", "y", "z")  # the trace branch, then the diagonal entry taken
+
+
+def _eigen_branch(R):
+    tr = R[0][0] + R[1][1] + R[2][2]
+    if tr > 0:
+        return "w"
+    i = 0
+    if R[1][1] > R[0][0]:
+        i = 1
+    if R[2][2] > R[i][i]:
+        i = 2
+    return BRANCHES[1 + i]
+
+
+def frame_quat(R, branch=None):
+    """Eigen 3.4's rotation-matrix-to-quaternion conversion (quaternionbase_assign_impl<Other, 3, 3>) followed
+    literally on any 3x3 matrix: ((w, x, y, z), branch).  `branch` ("w", "x", "y", "z"): under that branch"""
+    if branch is None:
+        branch = _eigen_branch(R)
+    if branch == "w":
+        t = M.sqrt(R[0][0] + R[1][1] + R[2][2] + 1)
+        return [t / 2, (R[2][1] - R[1][2]) / (2 * t), (R[0][2] - R[2][0]) / (2 * t), (R[1][0] - R[0][1]) / (2 * t)], branch
+    i = BRANCHES.index(branch) - 1
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = M.sqrt(R[i][i] - R[j][j] - R[k][k] + 1)
+    v = [M.mpf(0)] * 3
+    v[i] = t / 2
+    v[j] = (R[j][i] + R[i][j]) / (2 * t)
+    v[k] = (R[k][i] + R[i][k]) / (2 * t)
+    return [(R[k][j] - R[j][k]) / (2 * t)] + v, branch
+
+
+def branch_decisions(R):
+    """[(margin, other)] of the comparisons `frame_quat` made on R: |trace|, then (trace <= 0) |R11 - R00| and
+    |R22 - R_ii|; `other` is the branch the conversion takes when that comparison alone goes the other way"""
+    d = [R[0][0], R[1][1], R[2][2]]
+    tr = d[0] + d[1] + d[2]
+
+    def diag(first, second):  # the branch when the two diagonal comparisons come out as given
+        i = 1 if first else 0
+        return BRANCHES[1 + (2 if second(i) else i)]
+
+    natural = lambda i: d[2] > d[i]  # noqa: E731
+    if tr > 0:
+        return [(abs(tr), diag(d[1] > d[0], natural))]
+    i = 1 if d[1] > d[0] else 0
+    return [(abs(tr), "w"), (abs(d[1] - d[0]), diag(not d[1] > d[0], natural)),
+            (abs(d[2] - d[i]), diag(d[1] > d[0], lambda i: not d[2] > d[i]))]
 
 
 def quat_mul(a, b):
@@ -179,32 +306,14 @@ def goal_quat(gq):
     toRotationMatrix, which does not normalise (a quaternion of norm s gives s^2 R + (1 - s^2) I), and
     angular_distance re-derives a quaternion from that matrix (src/goal.cpp:22-23) by Eigen's branches (the trace
     when it is > 0, else the largest diagonal entry) -- not a multiple of the given one unless it is unit"""
-    w, x, y, z = (mpf(v) for v in gq)
-    R = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
-    tr = R[0][0] + R[1][1] + R[2][2]
-    if tr > 0:
-        t = M.sqrt(tr + 1)
-        return [t / 2, (R[2][1] - R[1][2]) / (2 * t), (R[0][2] - R[2][0]) / (2 * t), (R[1][0] - R[0][1]) / (2 * t)]
-    i = 0
-    if R[1][1] > R[0][0]:
-        i = 1
-    if R[2][2] > R[i][i]:
-        i = 2
-    j, k = (i + 1) % 3, (i + 2) % 3
-    t = M.sqrt(R[i][i] - R[j][j] - R[k][k] + 1)
-    v = [M.mpf(0)] * 3
-    v[i] = t / 2
-    v[j] = (R[j][i] + R[i][j]) / (2 * t)
-    v[k] = (R[k][i] + R[i][k]) / (2 * t)
-    return [(R[k][j] - R[j][k]) / (2 * t)] + v
+    return frame_quat(quat_matrix(*(mpf(v) for v in gq)))[0]
 
 
-def angular_distance(R, gq):
-    """Eigen angularDistance between the exact frame R and the goal quaternion (w, x, y, z) as upstream takes it
-    (`goal_quat`); angularDistance itself does not depend on the norm of either quaternion"""
-    return quat_angle(matrix_to_quat(R), goal_quat(gq))
+def angular_distance(R, gq, branch=None):
+    """Eigen angularDistance between the exact frame R -- its quaternion by Eigen's branches (`frame_quat`; `branch`:
+    under that branch) -- and the goal quaternion (w, x, y, z) as upstream takes it (`goal_quat`); angularDistance
+    itself does not depend on the norm of either quaternion"""
+    return quat_angle(frame_quat(R, branch)[0], goal_quat(gq))
 
 
 def linear_distance(t, goal_t):
@@ -258,15 +367,21 @@ class Cost:
     lin: list           # per tip: |goal - frame| (mpf)
     ang: list           # per tip: angular distance (mpf)
     goal_terms: list    # [(weight, unweighted cost)] of the joint goals
+    frames: list = None  # per tip: (position, matrix) (mpf), the exact FK
+    quats: list = None   # per tip: (the frame's quaternion, the goal's) as the angle took them (mpf)
+    goal: np.ndarray = None  # [n_tips][7], the goal as given
 
 
-def cost(chain, params, goal, seed, q):
+def cost(chain, params, goal, seed, q, branch=None):
     """make_cost_fn and make_is_solution_test_fn (src/goal.cpp:163-203) of one (goal, seed, q); `goal` holds
-    x y z qw qx qy qz per tip frame, `params` the fields of pick_ik_amd.default_params()"""
+    x y z qw qx qy qz per tip frame, `params` the fields of pick_ik_amd.default_params().  `branch`: the tip frames'
+    quaternions under that branch of `frame_quat` (one for every tip, or one per tip) instead of Eigen's choice"""
     g = np.asarray(goal, dtype=np.float64).reshape(-1, 7)
     frames = fk(chain, q)
     lin = [linear_distance(t, gk[:3]) for (t, _), gk in zip(frames, g)]
-    ang = [angular_distance(R, gk[3:]) for (_, R), gk in zip(frames, g)]
+    br = branch if isinstance(branch, (list, tuple)) else [branch] * len(frames)
+    quats = [(frame_quat(R, b)[0], goal_quat(gk[3:])) for (_, R), gk, b in zip(frames, g, br)]
+    ang = [quat_angle(a, b) for a, b in quats]
     c = sum((pose_cost(a, b, params.position_scale, params.rotation_scale) for a, b in zip(lin, ang)), M.mpf(0))
     terms = joint_goal_terms(chain, params, seed, q)
     c += sum((v * mpf(w) ** 2 for w, v in terms), M.mpf(0))
@@ -279,48 +394,106 @@ def cost(chain, params, goal, seed, q):
     for w, v in terms:
         if not v * mpf(w) ** 2 < mpf(params.cost_threshold) ** 2:
             sol = False
-    return Cost(c, sol, lin, ang, terms)
+    return Cost(c, sol, lin, ang, terms, frames, quats, g)
+
+
+def _extent(chain, v, q, given=False):
+    """the largest |q_v|: from the variable's limits, or from `q` (one joint vector or several) where it is larger;
+    `given`: from `q` alone where there is one"""
+    ext = max(abs(float(chain.qmin[v])), abs(float(chain.qmax[v])))
+    if q is not None:
+        at = float(np.max(np.abs(np.asarray(q, dtype=np.float64).reshape(-1, chain.dof)[:, v])))
+        ext = at if given else max(ext, at)
+    return ext
+
+
+def _walk(chain, p, q):
+    """(R, kappa) of one path: the translations of its steps, each times the product of the factors kappa =
+    max(1, 2 s^2 - 1) of the floating steps in front of it, and that product at the tip"""
+    r, K = 0.0, 1.0
+
+    def mimics(after):
+        nonlocal r
+        for m in p.mimic:
+            if int(m.after_variable) == after:
+                r += K * float(np.linalg.norm(np.asarray(m.origin_xyz_rpy, dtype=np.float64)[:3]))
+                if int(m.joint_type) == robots.PRISMATIC:
+                    r += K * (abs(m.multiplier) * _extent(chain, int(m.master_variable), q) + abs(m.offset))
+
+    mimics(-1)
+    for j, t in enumerate(p.joint_type):
+        t, v = int(t), int(p.variable[j])
+        if t not in robots.FLOATING[1:]:  # (the other six variables of a floating joint carry no origin)
+            r += K * float(np.linalg.norm(p.origin_xyz_rpy[j][:3]))
+        if t in (robots.PRISMATIC, robots.PLANAR_X, robots.PLANAR_Y):
+            r += K * _extent(chain, v, q)
+        if t == robots.FLOATING_TX:
+            r += K * math.sqrt(sum(_extent(chain, int(p.variable[j + i]), q, True) ** 2 for i in range(3)))
+        if t == robots.FLOATING_RW:
+            K *= max(1.0, 2.0 * sum(_extent(chain, int(p.variable[j - i]), q, True) ** 2 for i in range(4)) - 1.0)
+        if t not in robots.FLOATING[:-1]:
+            mimics(v)
+    return r + K * float(np.linalg.norm(p.tip_xyz_rpy[:3])), K
 
 
 def reach(chain, q=None):
     """R of the error bounds: the sum of the norms of the origin and tip translations plus the prismatic extents
-    (the largest |q| of a prismatic variable, from its limits or from `q`)"""
-    r = 0.0
-    for p in paths(chain):
-        r += sum(float(np.linalg.norm(o[:3])) for o in p.origin_xyz_rpy) + float(np.linalg.norm(p.tip_xyz_rpy[:3]))
-        for j, t in enumerate(p.joint_type):
-            if int(t) in (robots.PRISMATIC, robots.PLANAR_X, robots.PLANAR_Y):
-                v = int(p.variable[j])
-                ext = max(abs(float(chain.qmin[v])), abs(float(chain.qmax[v])))
-                if q is not None:
-                    ext = max(ext, float(np.max(np.abs(np.asarray(q, dtype=np.float64).reshape(-1, chain.dof)[:, v]))))
-                r += ext
-    return r
+    (the largest |q| of a prismatic variable, from its limits or from `q`; |multiplier| times its master's plus
+    |offset| for a prismatic mimic joint) and a floating joint's translation extent.  A floating step's matrix
+    s^2 R' + (1 - s^2) I (s the norm of its quaternion variables) is normal, of 2-norm kappa = max(1, 2 s^2 - 1):
+    every translation behind it counts kappa times (`scaling`).  A floating joint's seven values are those of `q`
+    where it is given (the bound of that sample), their limits otherwise (kappa <= 7 for components in [-1, 1])"""
+    return sum(_walk(chain, p, q)[0] for p in paths(chain))
 
 
-def pose7(chain, q):
-    """fk as doubles: x y z qw qx qy qz per tip (w >= 0), shape [7] or [n_tips][7] like Solver.fk"""
+def scaling(chain, q=None):
+    """the largest product of the floating steps' factors kappa = max(1, 2 s^2 - 1) along a tip path (1 without a
+    floating joint): what a rounding error in front of the tip is multiplied by on its way there"""
+    return max(_walk(chain, p, q)[1] for p in paths(chain))
+
+
+def pose7(chain, q, eigen_sign=False):
+    """fk as doubles: x y z qw qx qy qz per tip, shape [7] or [n_tips][7] like Solver.fk; the quaternion by Eigen's
+    branches (`frame_quat`), with w >= 0 -- or as Eigen leaves it (`eigen_sign`: the component its branch takes the
+    square root for is the positive one), which is what Solver.fk returns"""
     out = []
     for t, R in fk(chain, q):
-        out.append([float(x) for x in t] + [float(x) for x in matrix_to_quat(R)])
+        qt = frame_quat(R)[0]
+        if qt[0] < 0 and not eigen_sign:
+            qt = [-x for x in qt]
+        out.append([float(x) for x in t] + [float(x) for x in qt])
     out = np.array(out)
     return out if hasattr(chain, "tips") else out[0]
 
 
 def pose_errors(chain, q, pose):
     """(position error [m], orientation error [rad]) per tip of a double pose (x y z qw qx qy qz, either sign of the
-    quaternion) against the exact FK"""
+    quaternion) against the exact FK.  For chains whose frames are rotations: the returned quaternion is normalised,
+    which means nothing behind a floating joint (`component_errors`)"""
     pose = np.asarray(pose, dtype=np.float64).reshape(-1, 7)
     out = []
     for (t, R), p in zip(fk(chain, q), pose):
         dp = float(M.sqrt(sum((a - mpf(b)) ** 2 for a, b in zip(t, p[:3]))))
-        qe = matrix_to_quat(R)
+        qe = frame_quat(R)[0]
         qp = [mpf(x) for x in p[3:]]
         # the angle between the two orientations, from the unnormalised double quaternion (its norm error is part
         # of the error: |q| - 1 enters every rotation the caller builds from it)
         n = M.sqrt(sum(x * x for x in qp))
         ang = quat_angle([x / n for x in qp], qe)
         out.append((dp, float(ang), float(abs(n - 1))))
+    return out
+
+
+def component_errors(frames, pose, branch=None):
+    """(position error [m], the largest error of a quaternion component) per tip of a double pose (x y z qw qx qy qz
+    as Solver.fk returns it, Eigen's sign) against the exact frames [(position, matrix)], component by component;
+    `branch`: against the quaternion under that branch of `frame_quat`"""
+    pose = np.asarray(pose, dtype=np.float64).reshape(-1, 7)
+    out = []
+    for (t, R), p in zip(frames, pose):
+        dp = float(M.sqrt(sum((a - mpf(b)) ** 2 for a, b in zip(t, p[:3]))))
+        qe = frame_quat(R, branch)[0]
+        out.append((dp, float(max(abs(a - mpf(b)) for a, b in zip(qe, p[3:])))))
     return out
 
 

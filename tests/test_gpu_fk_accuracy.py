@@ -11,6 +11,11 @@ error analysis:
   cost         propagated: 2 s_p^2 |dp| e_p + s_p^2 e_p^2 + the same for the angle (whose error adds the two quaternion
                extractions and angle_of, 4e-15 rad) + 16 u of the cost
   verdict      may differ only where |dp| or the angle lies within its error of the threshold
+
+A mimic joint is one more step (D counts it); its value fl(m q + o) is off by <= 2 u (|m q| + |o|): an angle among the
+f_j for a revolute one, a length added to the position bound for a prismatic one.  Floating variables are no angles
+(no f_j); chains with a floating joint have bounds of their own (tests/test_gpu_floating_mimic_accuracy.py), which
+start from these.
 """
 import dataclasses
 import math
@@ -37,8 +42,11 @@ def solver(ch, flavour):
 def joint_terms(ch, q, flavour):
     """sum_j f_j of the bound (see the module docstring), per tip path"""
     f = 0.0
+    for m in getattr(ch, "mimic", ()):
+        if int(m.joint_type) == robots.REVOLUTE:
+            f += 2 * U * (abs(m.multiplier * q[int(m.master_variable)]) + abs(m.offset))
     for j, t in enumerate(ch.joint_type if not hasattr(ch, "tips") else np.zeros(ch.dof, np.int32)):
-        if int(t) in (robots.PRISMATIC, robots.PLANAR_X, robots.PLANAR_Y):
+        if int(t) in (robots.PRISMATIC, robots.PLANAR_X, robots.PLANAR_Y) + robots.FLOATING:
             continue
         if abs(q[j]) > 65536.0:
             f += 6e-16
@@ -48,9 +56,40 @@ def joint_terms(ch, q, flavour):
 
 
 def fk_bounds(ch, q, flavour):
-    d = max(len(p.variable) for p in H.paths(ch))
+    d = max(len(p.variable) + len(p.mimic) for p in H.paths(ch))
     a = 8 * (d + 2) * U + joint_terms(ch, q, flavour)
-    return a * H.reach(ch, q), a
+    slide = sum(2 * U * (abs(m.multiplier * q[int(m.master_variable)]) + abs(m.offset))
+                for m in getattr(ch, "mimic", ()) if int(m.joint_type) == robots.PRISMATIC)
+    return a * H.reach(ch, q) + slide * H.scaling(ch, q), a
+
+
+def has_floating(ch):
+    return any(int(t) in robots.FLOATING for p in H.paths(ch) for t in p.joint_type)
+
+
+def quat_bound(R, e_mat):
+    """the error of a component of Eigen's quaternion of a matrix known entrywise to e_mat (R: the exact one), see
+    tests/test_gpu_floating_mimic_accuracy.py"""
+    m = max(abs(float(x)) for row in R for x in row)
+    return 2 * (1 + m) * e_mat + 4 * U * (1 + m) ** 2
+
+
+def angle_bounds(ch, q, flavour, r):
+    """e_a per tip: the error of the angles of r = hp_reference.cost at q.  Frames that are rotations: the
+    orientation bound + EXTRACT.  Behind a floating joint (tests/test_gpu_floating_mimic_accuracy.py): from the
+    component errors of the two quaternions over their norms"""
+    a = fk_bounds(ch, q, flavour)[1]
+    if not has_floating(ch):
+        return [a + EXTRACT] * len(r.ang)
+    out = []
+    for (_, R), (qt, qg), g in zip(r.frames, r.quats, r.goal):
+        w, x, y, z = (float(v) for v in g[3:])
+        kg = max(1.0, 2 * (w * w + x * x + y * y + z * z) - 1)
+        eq = quat_bound(R, a * H.scaling(ch, q))
+        eg = quat_bound(H.quat_matrix(w, x, y, z), 7 * U * kg)
+        out.append(4 * eq / float(H.M.sqrt(sum(v * v for v in qt))) + 4 * eg / float(H.M.sqrt(sum(v * v for v in qg)))
+                   + EXTRACT)
+    return out
 
 
 def check_fk(ch, q, flavours=FLAVOURS, what=""):
@@ -163,9 +202,12 @@ def rotate(q, angle, axis):
 def goals_around(ch, q, rng):
     """goals 1e-12 .. 1e-2 away from the exact frame in position and in angle, at angle pi - 10^-k (near 180 degrees)
     and 2 pi / 3 (the relative rotation's trace near 0)"""
-    n = len(q)
-    g = np.array([H.pose7(ch, qi) for qi in q])
-    for i in range(n):
+    return goals_around_frames(np.array([H.pose7(ch, qi) for qi in q]), rng)
+
+
+def goals_around_frames(g, rng):
+    """`goals_around` of the poses g [n][7] (changed in place)"""
+    for i in range(len(g)):
         ax = rng.normal(size=3)
         ax /= np.linalg.norm(ax)
         kind = i % 4

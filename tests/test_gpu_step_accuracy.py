@@ -47,7 +47,7 @@ import pytest
 import pick_ik_amd as pk
 from pick_ik_amd import robots
 from tests import hp_reference as H
-from tests.test_gpu_fk_accuracy import EXTRACT, FLAVOURS, fk_bounds, solver
+from tests.test_gpu_fk_accuracy import EXTRACT, FLAVOURS, angle_bounds, fk_bounds, solver
 from tests.test_gpu_fuzz import random_chain
 
 pytestmark = pytest.mark.gpu
@@ -62,11 +62,10 @@ GOALS = dict(center_joints_weight=0.05, avoid_joint_limits_weight=0.1, minimal_d
 # ---------------------------------------------------------------------------------------------------------------
 def cost_bound(ch, p, fl, x, r):
     """e_c: the error of a flavour's cost at the joint vector x, r = hp_reference.cost there"""
-    ep, ea = fk_bounds(ch, x, fl)
-    ea += EXTRACT
+    ep = fk_bounds(ch, x, fl)[0]
     sp2, sr2 = max(p.position_scale, 0.0) ** 2, max(p.rotation_scale, 0.0) ** 2
     t = 16 * U * float(r.cost)
-    for lin, ang in zip(r.lin, r.ang):
+    for lin, ang, ea in zip(r.lin, r.ang, angle_bounds(ch, x, fl, r)):
         t += 2 * sp2 * float(lin) * ep + sp2 * ep * ep + 2 * sr2 * float(ang) * ea + sr2 * ea * ea
     return t
 
@@ -172,6 +171,7 @@ class Case:
     goal: np.ndarray
     seed: np.ndarray
     kw: dict
+    literal: bool = False  # a chain that the literal (pik_exact::) kernels serve in every flavour, at every step size
 
 
 REFS = {}  # (case id) -> [hp_reference.step without a given G]: computed once per module
@@ -201,11 +201,14 @@ def check(name, case, min_share=0.5, flavours=tuple(FLAVOURS)):
     lc_in = np.array([float(r.base.cost) for r in refs])
     bc_in = lc_in * rng.choice([0.5, 1.0, 2.0], size=n)
     report = {}
-    for fl in flavours:
-        s = solver(ch, fl)
+    for flavour in flavours:
+        # (the bounds of the kernels that serve the handle)
+        fl = "exact" if case.literal and flavour == "fast" else flavour
+        s = solver(ch, flavour)
         try:
-            if fl == "fast":
-                assert s.kernel_name(p).startswith("pik_exact::") == (h > LITERAL_ABOVE), (name, s.kernel_name(p))
+            if flavour == "fast":
+                assert s.kernel_name(p).startswith("pik_exact::") == (h > LITERAL_ABOVE or case.literal), \
+                    (name, s.kernel_name(p))
             local, best, lc, bc, G, imp = s.gd_step(p, goal, seed, q, best_in, lc_in, bc_in)
         finally:
             s.close()
@@ -243,7 +246,7 @@ def check(name, case, min_share=0.5, flavours=tuple(FLAVOURS)):
             np.testing.assert_array_equal(best[i], local[i] if better else best_in[i])
             assert bc[i] == (lc[i] if better else bc_in[i]), (name, fl, i)
         assert asserted >= min_share * n, (name, fl, asserted, n)
-        report[fl] = {k: round(v, 3) for k, v in worst.items()} | {"asserted": f"{asserted}/{n}"}
+        report[flavour] = {k: round(v, 3) for k, v in worst.items()} | {"asserted": f"{asserted}/{n}"}
     print(name, f"h={h:g}", report)
     return report
 

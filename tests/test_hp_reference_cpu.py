@@ -1,7 +1,10 @@
 """CPU: the high-precision reference (tests/hp_reference.py) itself -- against the oracle (math mode libm) at rounding
 level on the reference robots and on generated chains of 1..16 variables, and against the upstream known answers the
 oracle tests hold (tests/test_oracle_golden.py: frame tests, pose costs, the bio_ik samples, RR forward kinematics,
-the Panda's ready height, the minimal displacement factors)."""
+the Panda's ready height, the minimal displacement factors).  Chains with a floating joint or with mimic joints: the
+checks of tests/test_gpu_floating_mimic_accuracy.py -- FK, cost and verdict, step() stage by stage, the same samples,
+edges and bounds -- run here on the oracle in its three math modes, which the exact kernels repeat bit for bit."""
+import dataclasses
 import math
 
 import numpy as np
@@ -46,8 +49,31 @@ def test_fk_agrees_with_the_oracle(oracle_mod, name, make):
 
 
 def test_fk_rejects_what_it_does_not_model():
-    with pytest.raises(NotImplementedError):
-        H.fk(robots.floating_panda(), np.zeros(14))
+    """a floating joint is seven consecutive variables in MoveIt's order (tests/test_floating_cpu.py
+    test_chain_description_validates_floating_joints); a mimic joint follows a joint of its path"""
+    ch = robots.floating_panda()
+    assert len(H.paths(ch)) == 1
+    bad = ch.joint_type.copy()
+    bad[3] = robots.REVOLUTE  # a hole in the seven variables
+    with pytest.raises(ValueError, match="floating joint"):
+        H.fk(dataclasses.replace(ch, joint_type=bad), np.zeros(14))
+    bad = ch.joint_type.copy()
+    bad[:7] = bad[:7][::-1]  # wrong order
+    with pytest.raises(ValueError, match="floating joint"):
+        H.paths(dataclasses.replace(ch, joint_type=bad))
+    bad = ch.joint_type.copy()
+    bad[7:] = bad[:7]
+    bad[13] = robots.REVOLUTE  # a second joint cut off after six of its variables
+    with pytest.raises(ValueError, match="floating joint"):
+        H.paths(dataclasses.replace(ch, joint_type=bad))
+    m = robots.MimicJoint(after_variable=2, master_variable=8, origin_xyz_rpy=(0,) * 6, axis=(0, 0, 1))
+    with pytest.raises(NotImplementedError):  # between the variables of the floating joint
+        H.paths(dataclasses.replace(ch, mimic=(m,)))
+    with pytest.raises(ValueError, match="mimic joint"):
+        H.paths(dataclasses.replace(ch, mimic=(dataclasses.replace(m, after_variable=14),)))
+    with pytest.raises(ValueError, match="mimic joint"):
+        H.paths(dataclasses.replace(ch, mimic=(dataclasses.replace(m, after_variable=6, joint_type=robots.PLANAR_X),)))
+    assert len(H.paths(dataclasses.replace(ch, mimic=(dataclasses.replace(m, after_variable=6),)))[0].mimic) == 1
 
 
 def pose(t, q):
@@ -210,3 +236,227 @@ def test_off_unit_goal_quaternions_agree_with_the_oracle(oracle_mod):
         differs += abs(float(unit) - c) > 1e-9 * c
     assert branches == {True, False}, branches
     assert differs >= 8, differs
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# floating and mimic joints
+# ---------------------------------------------------------------------------------------------------------------
+MODES = ("libm", "portable", "fma")
+
+
+class OracleHandle:
+    """the oracle in one math mode behind the methods of pick_ik_amd.Solver that the accuracy checks call"""
+
+    def __init__(self, O, ch, mode):
+        self.O, self.o, self.mode = O, O.Oracle(ch), mode
+
+    def _p(self, p):
+        return self.O.Params.from_buffer_copy(bytes(p))
+
+    def fk(self, q):
+        with self.O.math_mode(self.mode):
+            return self.o.fk(q)
+
+    def cost(self, p, goal, seed, q):
+        with self.O.math_mode(self.mode):
+            r = [self.o.cost(self._p(p), goal[i], seed[i], q[i]) for i in range(len(q))]
+        return np.array([x[0][0] for x in r]), np.array([x[1][0] for x in r])
+
+    def gd_step(self, p, *a):
+        with self.O.math_mode(self.mode):
+            return self.o.gd_step(self._p(p), *a)
+
+    def solve_batch(self, p, goal, seed, rng_seed=0):
+        with self.O.math_mode(self.mode):
+            return self.o.solve_batch(self._p(p), goal, seed, rng_seed=rng_seed, num_threads=self.O.max_threads())
+
+    def kernel_name(self, p):
+        return "pik_exact::(the oracle)"
+
+    def close(self):
+        pass
+
+
+@pytest.fixture
+def F(oracle_mod, monkeypatch):
+    """tests/test_gpu_floating_mimic_accuracy.py with the oracle (flavour = math mode) in place of the GPU handles"""
+    from tests import test_gpu_fk_accuracy as A
+    from tests import test_gpu_floating_mimic_accuracy as F
+    from tests import test_gpu_step_accuracy as S
+    handle = lambda ch, mode: OracleHandle(oracle_mod, ch, mode)  # noqa: E731
+    monkeypatch.setattr(A, "solver", handle)
+    monkeypatch.setattr(S, "solver", handle)
+    F.handle = handle
+    return F
+
+
+def test_the_floating_chains_are_what_they_are_meant_to_be(F):
+    for name, where in (("floating_middle", "middle"), ("floating_end", "end")):
+        ch = F.chain(name)
+        at = int(np.flatnonzero(ch.joint_type == robots.FLOATING_TX)[0])
+        assert 1 <= ch.dof - 7 <= 9 and (0 < at < ch.dof - 7 if where == "middle" else at == ch.dof - 7), (name, at)
+    two = F.chain("two_tip_floating")
+    assert [list(t.variable[:7]) for t in two.tips] == [list(range(7))] * 2
+    for name in F.FLOATING:  # the edges are in every batch, and at least half of it is uniform
+        ch = F.chain(name)
+        q = F.samples(name, 21)
+        quat = F.floating_blocks(ch)[0][3:]
+        s2 = (q[11:, quat] ** 2).sum(axis=1)
+        assert (s2 == 4).any() and (s2 == 0).any() and ((s2 > 0) & (s2 < 1e-15)).any() and (abs(s2 - 1) < 1e-15).any()
+        margins = [min(float(m) for m, _ in H.branch_decisions(R)) for x in q[11:] for _, R in H.fk(ch, x)[:1]]
+        assert sum(m <= 1e-9 for m in margins) >= 2, (name, margins)  # (one by the trace, one by the diagonal)
+
+
+def test_the_two_tip_floating_chain_is_accepted(F):
+    """pikamd_create_multi validates the description before it looks for a device"""
+    import torch
+    import pick_ik_amd as pk
+    try:
+        pk.Solver(F.chain("two_tip_floating"), device=0).close()
+    except pk.PickIkAmdError as e:
+        assert not torch.cuda.is_available() and "no HIP device" in str(e), e
+
+
+@pytest.mark.parametrize("n", [21, 65])
+@pytest.mark.parametrize("name", ["floating_panda", "floating_middle", "floating_end", "two_tip_floating"])
+def test_floating_fk_agrees_with_the_oracle(F, name, n):
+    """position and every quaternion component, Eigen's sign and branch included"""
+    r = F.check_fk_components(name, n, flavours=MODES, handle=F.handle)
+    assert all(v["on_a_decision"] >= 1 for v in r.values()), r
+
+
+MIMIC_CASES = {f"{c[0]}_{c[1]}": c for c in __import__("tests.test_mimic_cpu", fromlist=["CASES"]).CASES}
+
+
+def mimic_chain(key):
+    """(the chain with the mimic joint, the chain with it as a variable, q -> that chain's q)"""
+    from tests import test_mimic_cpu as T
+    if key == "prismatic_two_in_a_row":
+        return T.prismatic_and_two_in_a_row()
+    name, k, master, mult, off = MIMIC_CASES[key]
+    full = robots.by_name(name)
+    ch, keep = T.with_mimic(None, full, k, master, mult, off)
+    return ch, full, lambda q: T.expand(q, keep, k, master, mult, off, full.dof)
+
+
+@pytest.mark.parametrize("key", list(MIMIC_CASES) + ["prismatic_two_in_a_row"])
+def test_mimic_fk_and_cost_agree_with_the_oracle(F, oracle_mod, key):
+    """the oracle's mimic step within the rounding bounds of the reference's, the cost and the verdict with it; and
+    the identity: the reference equals itself on the chain with the joint as an ordinary variable (the double
+    rounding of multiplier * master + offset, which that chain's joint vector holds, apart)"""
+    from tests import test_gpu_fk_accuracy as A
+    from tests import test_gpu_step_accuracy as S
+    ch, full, as_variables = mimic_chain(key)
+    rng = np.random.default_rng(17)
+    n = 16
+    q = rng.uniform(ch.qmin, ch.qmax, size=(n, ch.dof))
+    q[0], q[1] = ch.qmin, ch.qmax
+    print(key, A.check_fk(ch, q, flavours=MODES, what=key))
+    qf = as_variables(q)
+    slack = sum(2 * U * (abs(m.multiplier) * 3.8 + abs(m.offset)) for m in ch.mimic)
+    for i in range(n):
+        (t, R), (tf, Rf) = H.fk(ch, q[i])[0], H.fk(full, qf[i])[0]
+        assert max(abs(float(a - b)) for a, b in zip(t, tf)) <= slack * H.reach(full, qf[i]), (key, i)
+        assert max(abs(float(a - b)) for ra, rb in zip(R, Rf) for a, b in zip(ra, rb)) <= slack, (key, i)
+    import pick_ik_amd as pk
+    p = pk.default_params(**F.COST_KW)
+    goal = A.goals_around(ch, q, rng)
+    seed = rng.uniform(ch.qmin, ch.qmax, size=(n, ch.dof))
+    refs = [H.cost(ch, p, goal[i], seed[i], q[i]) for i in range(n)]
+    for mode in MODES:
+        c, sol = OracleHandle(oracle_mod, ch, mode).cost(p, goal, seed, q)
+        for i, r in enumerate(refs):
+            assert abs(c[i] - float(r.cost)) <= S.cost_bound(ch, p, "exact", q[i], r), (key, mode, i)
+            assert bool(sol[i]) == r.solution, (key, mode, i)
+
+
+@pytest.mark.parametrize("name,n", [("floating_panda", 33), ("floating_middle", 21), ("floating_end", 65),
+                                    ("two_tip_floating", 21), ("mimic_revolute", 33), ("mimic_prismatic", 65)])
+def test_floating_and_mimic_cost_agrees_with_the_oracle(F, name, n):
+    F.check_cost(name, n, flavours=MODES, handle=F.handle)
+
+
+@pytest.mark.parametrize("name,h,n", [("floating_panda", 1e-4, 33), ("floating_middle", 1e-8, 33),
+                                      ("floating_end", 0.3, 65), ("two_tip_floating", 1e-8, 21),
+                                      ("mimic_revolute", 0.3, 33), ("mimic_prismatic", 1e-4, 33)])
+def test_floating_and_mimic_step_agrees_with_the_oracle(F, name, h, n):
+    """tests/test_gpu_step_accuracy.py check() on the oracle's step(): every stage within its bound, the line search
+    asserted for at least half of the samples"""
+    from tests import test_gpu_step_accuracy as S
+    S.check(f"{name}-{h:g}-{n}", F.step_case(name, h, n), flavours=MODES)
+
+
+@pytest.mark.parametrize("how", ["local", "memetic"])
+@pytest.mark.parametrize("name", ["floating_panda", "mimic_revolute"])
+def test_floating_and_mimic_solves_agree_with_the_oracle(F, name, how):
+    """every SUCCESS a solution for the reference, every returned cost the reference's, and some problem solved"""
+    F.check_solves(name, how, flavours=MODES, handle=F.handle)
+
+
+def toy_floating_joint():
+    """a floating joint alone: no other joint, identity origins"""
+    return robots._chain("floating", np.zeros((7, 6)), np.tile([0.0, 0.0, 1.0], (7, 1)), np.zeros(6), [-1.0] * 7,
+                         [1.0] * 7, [1.0] * 7, joint_type=np.array(robots.FLOATING, dtype=np.int32))
+
+
+def test_a_floating_joint_alone_is_upstreams_formula():
+    """Translation(v0 v1 v2) * Quaterniond(v6, v3, v4, v5) (src/forward_kinematics.cpp:64-70), the quaternion not
+    normalised: for a quaternion of norm s and rotation R' (Rodrigues, from its angle and axis) the frame is
+    s^2 R' + (1 - s^2) I -- R' itself for s = 1 -- and the translation is the three variables"""
+    ch = toy_floating_joint()
+    rng = np.random.default_rng(8)
+    one = H.M.mpf(1)
+    for norm in [1.0] * 6 + [2.0] * 6 + [1e-3, 1e-8, 1e-30, 1e-200, 0.0]:
+        v = rng.normal(size=4)
+        v *= norm / np.linalg.norm(v)
+        x = np.concatenate([rng.uniform(-1, 1, size=3), v])
+        (t, R), = H.fk(ch, x)
+        assert [float(a) for a in t] == list(x[:3])
+        qx, qy, qz, qw = (H.mpf(a) for a in v)  # (the variables hold x y z w)
+        s2 = qw * qw + qx * qx + qy * qy + qz * qz
+        nv = H.M.sqrt(qx * qx + qy * qy + qz * qz)
+        Rp = H.rodrigues([qx / nv, qy / nv, qz / nv], 2 * H.M.atan2(nv, qw)) if nv > 0 else H._ident()
+        for i in range(3):
+            for j in range(3):
+                want = s2 * Rp[i][j] + (1 - s2) * (one if i == j else 0)
+                assert abs(R[i][j] - want) <= H.M.mpf(2) ** -120 * max(1, s2), (norm, i, j)
+        if norm == 1.0:
+            assert max(abs(float(R[i][j] - Rp[i][j])) for i in range(3) for j in range(3)) <= 8 * U
+        if norm < 1e-7:  # the identity to rounding: the trace branch, w = 1
+            qt, branch = H.frame_quat(R)
+            assert branch == "w" and abs(float(qt[0]) - 1) <= 2 * norm ** 2
+
+
+def test_frame_quat_on_rotations_is_matrix_to_quat():
+    """for an exact rotation Eigen's branches give the unit quaternion of matrix_to_quat (the largest of the four
+    candidates) up to sign, on every branch: the accuracy tests of the other chains do not move"""
+    rng = np.random.default_rng(9)
+    seen = set()
+    for name in ("panda", "ur5", "torso_dual_arm"):
+        ch = robots.by_name(name)
+        for x in rng.uniform(ch.qmin, ch.qmax, size=(40, ch.dof)):
+            for _, R in H.fk(ch, x):
+                a, branch = H.frame_quat(R)
+                b = H.matrix_to_quat(R)
+                sign = 1 if a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] > 0 else -1
+                assert max(abs(float(x - sign * y)) for x, y in zip(a, b)) <= 1e-35, (name, branch)
+                assert a["wxyz".index(branch)] > 0
+                seen.add(branch)
+                for forced in "wxyz":  # (any branch whose square root does not vanish)
+                    c = H.frame_quat(R, forced)[0]
+                    if abs(c["wxyz".index(forced)]) > 1e-3:
+                        assert max(abs(abs(float(x)) - abs(float(y))) for x, y in zip(a, c)) <= 1e-30
+    assert seen == set("wxyz"), seen
+
+
+def test_branch_decisions():
+    """the margins of the comparisons taken, and where the other outcome of each leads"""
+    d = lambda a, b, c: [[H.mpf(a), 0, 0], [0, H.mpf(b), 0], [0, 0, H.mpf(c)]]  # noqa: E731
+    assert H.frame_quat(d(1, 1, 1))[1] == "w"
+    assert [(float(m), o) for m, o in H.branch_decisions(d(0.5, -0.25, -0.125))] == [(0.125, "x")]
+    assert H.frame_quat(d(0.25, -0.5, -0.75))[1] == "x"
+    assert [(float(m), o) for m, o in H.branch_decisions(d(0.25, -0.5, -0.75))] == [(1.0, "w"), (0.75, "y"), (1.0, "z")]
+    assert H.frame_quat(d(-0.5, -0.5, -0.5))[1] == "x"  # ties stay with the earlier entry, a trace of 0 goes by diagonal
+    assert H.frame_quat(d(0.5, 0.0, -0.5))[1] == "x"
+    assert [o for _, o in H.branch_decisions(d(-0.5, -0.25, 0.5))] == ["w", "z", "y"]
+    assert H.frame_quat(d(-0.5, -0.25, 0.5))[1] == "z"

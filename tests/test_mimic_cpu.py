@@ -46,24 +46,35 @@ def test_oracle_mimic_step_equals_the_joint_as_a_variable(oracle_mod, name, k, m
     np.testing.assert_array_equal(a, b)
 
 
-def test_prismatic_mimic_and_two_in_a_row(oracle_mod):
-    O = oracle_mod
+def prismatic_and_two_in_a_row():
+    """(the chain with two mimic joints, the five-joint chain with them as variables, expand(q)): joints 1
+    (prismatic) and 2 both follow variable 0; variables: 0, 3, 4"""
     origins = [[0, 0, 0.2, 0, 0, 0], [0.1, 0, 0, 0.3, 0, 0], [0, 0.2, 0, 0, 0.4, 0], [0.3, 0, 0, 0, 0, 0.5], [0, 0, 0.1, 0.2, 0, 0]]
     axes = [[0, 0, 1], [1, 0, 0], [0, 1, 0.2], [0, 1, 0], [0, 0, 1]]
     jt = np.array([0, 1, 0, 0, 0], np.int32)
     full = robots._chain("f", origins, axes, [0.1, 0, 0, 0, 0, 0], [-1.5] * 5, [1.5] * 5, [1] * 5, joint_type=jt)
-    # joints 1 (prismatic) and 2 both follow variable 0; variables: 0, 3, 4
     keep = [0, 3, 4]
     ms = (robots.MimicJoint(0, 0, tuple(origins[1]), tuple(axes[1]), 0.1, 0.05, joint_type=1),
           robots.MimicJoint(0, 0, tuple(origins[2]), tuple(axes[2]), -1.2, 0.0, joint_type=0))
     ch = robots._chain("m", np.array(origins)[keep], np.array(axes)[keep], [0.1, 0, 0, 0, 0, 0], [-1.5] * 3, [1.5] * 3, [1] * 3)
     ch = dataclasses.replace(ch, mimic=ms)
+
+    def as_variables(q):
+        qf = np.zeros((len(q), 5))
+        qf[:, keep] = q
+        qf[:, 1] = 0.1 * q[:, 0] + 0.05
+        qf[:, 2] = -1.2 * q[:, 0] + 0.0
+        return qf
+
+    return ch, full, as_variables
+
+
+def test_prismatic_mimic_and_two_in_a_row(oracle_mod):
+    O = oracle_mod
+    ch, full, as_variables = prismatic_and_two_in_a_row()
     rng = np.random.default_rng(0)
     q = rng.uniform(-1.5, 1.5, size=(40, 3))
-    qf = np.zeros((40, 5))
-    qf[:, keep] = q
-    qf[:, 1] = 0.1 * q[:, 0] + 0.05
-    qf[:, 2] = -1.2 * q[:, 0] + 0.0
+    qf = as_variables(q)
     for mode in ("portable", "fma"):
         with O.math_mode(mode):
             np.testing.assert_array_equal(O.Oracle(ch).fk(q), O.Oracle(full).fk(qf))
