@@ -553,6 +553,25 @@ int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int
  * of every problem on the chip at once, a small finalize kernel behind them) */
 const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t B,
                                       int32_t max_attempts, int32_t* attempts_in_flight);
+/* ---- Device-side choice of the regime (option device_regime) -------------------------------------
+ * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
+ * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes
+ * the latency schedule (most lanes per elite that fit the chip) unless the calls in flight on the handle's OTHER
+ * slots hold at least regime_threshold problems (default: SIMD count * 32 / pow2ceil(elites), half of what puts a
+ * one-lane wavefront on every SIMD), in which case it takes the throughput schedule (one lane per elite).  Like every scheduling option
+ * this changes no result.  device_regime = 0: the regime is chosen once per call on the host, from the number of
+ * other calls in flight when it is enqueued.
+ *
+ * pikamd_debug_regime (tests, profile scripts; synchronises the device): for the LAST solve call on `slot`,
+ * *n_passes = the passes the routed launcher cut it into, or -1 when the call was not routed (host rule); for pass
+ * k < min(*n_passes, max_passes): survivors[k] = problems the pass started with, others_load[k] = the load the
+ * router saw on the other slots, variant[k] = the kernel variant it chose (5 / 4 / 3 / 2: 16 / 8 / 4 / 2 lanes per
+ * elite, 1: one lane, 7: one lane, two wavefronts per SIMD; 0: no survivor, no kernel ran).  publish_load >= 0: first
+ * sets the load `slot` publishes to the other slots' routers to that many problems (a slot with no call in flight:
+ * an artificial load; a routed call on the slot overwrites it); < 0: leaves it.  Any of the output pointers may be
+ * NULL with max_passes = 0. */
+int32_t pikamd_debug_regime(pikamd_solver* s, int32_t slot, int64_t publish_load, int32_t max_passes,
+                            int32_t* n_passes, uint32_t* survivors, uint32_t* others_load, int32_t* variant);
 /* [host-api-end] */
 
 #ifdef __cplusplus

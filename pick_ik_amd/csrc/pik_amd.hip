@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pik_path_ops.hpp"
+#include "pik_route_ops.hpp"
 #include "pik_search_ops.hpp"
 #include "pik_solver.hpp"
 #include "pik_urdf.hpp"
@@ -61,6 +62,13 @@ PIK_LITERAL_SEARCH_OPS(5) PIK_LITERAL_SEARCH_OPS(6) PIK_LITERAL_SEARCH_OPS(7) PI
 PIK_LITERAL_SEARCH_OPS(9) PIK_LITERAL_SEARCH_OPS(10) PIK_LITERAL_SEARCH_OPS(11) PIK_LITERAL_SEARCH_OPS(12)
 PIK_LITERAL_SEARCH_OPS(13) PIK_LITERAL_SEARCH_OPS(14) PIK_LITERAL_SEARCH_OPS(15) PIK_LITERAL_SEARCH_OPS(16)
 #undef PIK_LITERAL_SEARCH_OPS
+// (... and the routed launcher, pik_route_inst.hip: built for every flavour of the product library)
+#define PIK_FLAVOUR_ROUTE_OPS(N) const void* route_ops_d##N();
+PIK_FLAVOUR_ROUTE_OPS(1) PIK_FLAVOUR_ROUTE_OPS(2) PIK_FLAVOUR_ROUTE_OPS(3) PIK_FLAVOUR_ROUTE_OPS(4)
+PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_FLAVOUR_ROUTE_OPS(8)
+PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
+PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
+#undef PIK_FLAVOUR_ROUTE_OPS
 } // namespace pik_exact
 // ... and the kernels specialised for the common configuration (flavour -DPIK_COMMON=1, namespace pik_common;
 // pik_math.hpp says what that is and what it buys)
@@ -71,6 +79,12 @@ PIK_COMMON_OPS(1) PIK_COMMON_OPS(2) PIK_COMMON_OPS(3) PIK_COMMON_OPS(4) PIK_COMM
 PIK_COMMON_OPS(7) PIK_COMMON_OPS(8) PIK_COMMON_OPS(9) PIK_COMMON_OPS(10) PIK_COMMON_OPS(11) PIK_COMMON_OPS(12)
 PIK_COMMON_OPS(13) PIK_COMMON_OPS(14) PIK_COMMON_OPS(15) PIK_COMMON_OPS(16)
 #undef PIK_COMMON_OPS
+#define PIK_FLAVOUR_ROUTE_OPS(N) const void* route_ops_d##N();
+PIK_FLAVOUR_ROUTE_OPS(1) PIK_FLAVOUR_ROUTE_OPS(2) PIK_FLAVOUR_ROUTE_OPS(3) PIK_FLAVOUR_ROUTE_OPS(4)
+PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_FLAVOUR_ROUTE_OPS(8)
+PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
+PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
+#undef PIK_FLAVOUR_ROUTE_OPS
 } // namespace pik_common
 // ... and the same with the joint goals left in (-DPIK_NO_GOALS=0): BASELINE config 3's kind of call
 namespace pik_common_goals {
@@ -80,6 +94,12 @@ PIK_COMMON_OPS(1) PIK_COMMON_OPS(2) PIK_COMMON_OPS(3) PIK_COMMON_OPS(4) PIK_COMM
 PIK_COMMON_OPS(7) PIK_COMMON_OPS(8) PIK_COMMON_OPS(9) PIK_COMMON_OPS(10) PIK_COMMON_OPS(11) PIK_COMMON_OPS(12)
 PIK_COMMON_OPS(13) PIK_COMMON_OPS(14) PIK_COMMON_OPS(15) PIK_COMMON_OPS(16)
 #undef PIK_COMMON_OPS
+#define PIK_FLAVOUR_ROUTE_OPS(N) const void* route_ops_d##N();
+PIK_FLAVOUR_ROUTE_OPS(1) PIK_FLAVOUR_ROUTE_OPS(2) PIK_FLAVOUR_ROUTE_OPS(3) PIK_FLAVOUR_ROUTE_OPS(4)
+PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_FLAVOUR_ROUTE_OPS(8)
+PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
+PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
+#undef PIK_FLAVOUR_ROUTE_OPS
 } // namespace pik_common_goals
 #endif
 
@@ -91,6 +111,16 @@ namespace {
 struct SolverExt : pikamd_solver {
     int search_schedule = pik::SEARCH_ADAPTIVE;
     pik::DevBuf search_rows[pik::N_SLOTS];
+    // the routed launcher (pik_route.hpp): the option device_regime (1: the regime of a pass is chosen on the device
+    // when the pass starts; 0: on the host when the call is enqueued, launch_solve's rule), the option
+    // regime_threshold (0: the default) and, per slot, the passes the routed launcher enqueued for the last call
+    // (-1: the call was launch_solve's) -- what pikamd_debug_regime reads the slot's record by
+    int device_regime = 1;
+    long long regime_threshold = 0;
+    int routed_passes[pik::N_SLOTS];
+    SolverExt() {
+        for (int& v : routed_passes) v = -1;
+    }
 };
 SolverExt* ext_of(pikamd_solver* s) { return static_cast<SolverExt*>(s); }
 const SolverExt* ext_of(const pikamd_solver* s) { return static_cast<const SolverExt*>(s); }
@@ -185,6 +215,55 @@ const pik::LaunchOps* solve_ops_of(const pikamd_solver* s, const pikamd_params* 
     (void)pk;
 #endif
     return ops_of(s, p);
+}
+
+// The routed launcher of one solve call (pik_route.hpp: the regime of every pass chosen on the device), in the
+// flavour solve_ops_of picks -- or null: the call is launch_solve's.  Routed are memetic calls on one tip frame with
+// one species, nothing forced (lanes per elite, their schedule, the regime) and the option device_regime on; whether
+// the call has a compaction pass to route the launcher finds out itself (RouteCtx::served).  The verification library
+// has no routed launcher.
+[[maybe_unused]] const pik::RouteOps* route_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
+#if !defined(PIK_STRICT)
+    const pik::SolverOptions& o = s->opt;
+    if (!ext_of(s)->device_regime || p->mode != 0 || s->n_tips != 1 || p->memetic_num_threads > 1 || o.lpe != 0 ||
+        o.n_sched != 0 || o.regime != 0)
+        return nullptr;
+    const bool common = common_eligible(s, p, pk), goals = pk.goal_mask != 0, literal = needs_literal(s, p);
+    const void* r = nullptr;
+    switch (s->chain.dof) {
+#define PIK_ROUTE_CASE(N)                                                                                             \
+    case N:                                                                                                           \
+        r = common ? (goals ? pik_common_goals::route_ops_d##N() : pik_common::route_ops_d##N())                      \
+                   : literal ? pik_exact::route_ops_d##N() : static_cast<const void*>(pik::route_ops_d##N());         \
+        break;
+        PIK_ROUTE_CASE(1) PIK_ROUTE_CASE(2) PIK_ROUTE_CASE(3) PIK_ROUTE_CASE(4) PIK_ROUTE_CASE(5) PIK_ROUTE_CASE(6)
+        PIK_ROUTE_CASE(7) PIK_ROUTE_CASE(8) PIK_ROUTE_CASE(9) PIK_ROUTE_CASE(10) PIK_ROUTE_CASE(11) PIK_ROUTE_CASE(12)
+        PIK_ROUTE_CASE(13) PIK_ROUTE_CASE(14) PIK_ROUTE_CASE(15) PIK_ROUTE_CASE(16)
+#undef PIK_ROUTE_CASE
+        default: break;
+    }
+    return static_cast<const pik::RouteOps*>(r);
+#else
+    (void)s, (void)p, (void)pk;
+    return nullptr;
+#endif
+}
+
+// one solve call: the routed launcher where the call is of its kind, launch_solve otherwise
+int run_solve(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, pik::BatchRecord* rec, int n,
+              unsigned long long rng_seed, hipStream_t stream, int slot) {
+    SolverExt* x = ext_of(s);
+    if (const pik::RouteOps* r = route_ops_of(s, p, pk)) {
+        pik::RouteCtx ctx;
+        ctx.threshold = x->regime_threshold;
+        if (int rc = r->solve(s, p, pk, rec, n, rng_seed, stream, slot, &ctx)) return rc;
+        if (ctx.served) {
+            x->routed_passes[slot] = ctx.n_passes;
+            return 0;
+        }
+    }
+    x->routed_passes[slot] = -1;
+    return solve_ops_of(s, p, pk)->solve(s, p, pk, rec, n, rng_seed, stream, slot, false);
 }
 
 int no_kernels(int dof) {
@@ -290,8 +369,9 @@ static int32_t create_solver(const pik::ChainHost* chains, int n_tips, int32_t d
     s->n_tips = n_tips;
     for (int k = 1; k < n_tips; ++k) s->more[k - 1] = chains[k];
     const size_t table_bytes = sizeof(pik::BatchRecord) * PIKAMD_MAX_BATCHES * pik::TABLE_RING;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->counters), pik::COUNTER_BLOCK * pik::N_SLOTS);
-    if (e == hipSuccess) e = hipMemset(s->counters, 0, pik::COUNTER_BLOCK * pik::N_SLOTS);
+    // (the counter blocks of the slots + the routed launcher's variant counters, loads and records behind them)
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->counters), pik::COUNTERS_BYTES);
+    if (e == hipSuccess) e = hipMemset(s->counters, 0, pik::COUNTERS_BYTES);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->consts_dev), pik::CONSTS_STRIDE * pik::N_SLOTS);
     if (e == hipSuccess)
         e = hipHostMalloc(reinterpret_cast<void**>(&s->consts_host), pik::CONSTS_STRIDE * pik::N_SLOTS, hipHostMallocDefault);
@@ -606,7 +686,7 @@ static int32_t solve_records(pikamd_solver* s, const pikamd_params* p, pik::Batc
     if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(s->device));
-    if (!s->opt.soa) return solve_ops_of(s, p, pk)->solve(s, p, pk, rec, n, rng_seed, stream, slot, false);
+    if (!s->opt.soa) return run_solve(s, p, pk, rec, n, rng_seed, stream, slot);
     // joint vectors structure-of-arrays: seed / initial guess are transposed into scratch in front of the
     // kernels, the solutions out of scratch behind them, all on the call's stream
     const int D = s->chain.dof;
@@ -645,7 +725,7 @@ static int32_t solve_records(pikamd_solver* s, const pikamd_params* p, pik::Batc
         rec[k].solution = w;
         w += (size_t)B * D;
     }
-    if (int rc = solve_ops_of(s, p, pk)->solve(s, p, pk, rec, n, rng_seed, stream, slot, false)) return rc;
+    if (int rc = run_solve(s, p, pk, rec, n, rng_seed, stream, slot)) return rc;
     for (int k = 0; k < n; ++k)
         if (int rc = move(rec[k].solution, user_solution[k], rec[k].B, 0)) return rc;
     return 0;
@@ -968,6 +1048,21 @@ int32_t pikamd_set_option(pikamd_solver* s, const char* name, const char* value)
         if (v == "sequential") { sched = pik::SEARCH_SEQUENTIAL; return 0; }
         if (v == "parallel") { sched = pik::SEARCH_PARALLEL; return 0; }
         return fail(PIKAMD_EINVAL, "search_schedule: expected 'adaptive', 'sequential' or 'parallel', got '%s'", v.c_str());
+    }
+    if (n == "device_regime") { // "1" (default): the regime of a pass is chosen on the device when it starts; "0": on the host
+        int x = 1;
+        if (!pik::parse_device_regime(v.c_str(), &x))
+            return fail(PIKAMD_EINVAL, "device_regime: expected '0' or '1', got '%s'", v.c_str());
+        ext_of(s)->device_regime = x;
+        return 0;
+    }
+    if (n == "regime_threshold") { // problems the OTHER slots hold from which a pass takes the throughput schedule ("" / 0: default)
+        if (v.empty()) { ext_of(s)->regime_threshold = 0; return 0; }
+        std::vector<int> x;
+        if (!ints(v, ',', x) || x.size() != 1 || x[0] < 0)
+            return fail(PIKAMD_EINVAL, "regime_threshold: expected a number of problems >= 0, got '%s'", v.c_str());
+        ext_of(s)->regime_threshold = x[0];
+        return 0;
     }
     if (n == "regime") {
         if (v.empty() || v == "adaptive") { o.regime = 0; return 0; }
@@ -1617,6 +1712,34 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
         snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_wide_kernel<%d,%d,%s>", ns, dof, lanes,
                  s->n_tips > 1 ? "true" : "false");
     return m->kernel_name;
+}
+
+// ---- the routed launcher's record (tests, profile scripts) ----------------------------------------
+
+int32_t pikamd_debug_regime(pikamd_solver* s, int32_t slot, int64_t publish_load, int32_t max_passes,
+                            int32_t* n_passes, uint32_t* survivors, uint32_t* others_load, int32_t* variant) {
+    if (int rc = check_solver(s)) return rc;
+    if (slot < 0 || slot >= pik::N_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (max_passes < 0 || (max_passes > 0 && (!survivors || !others_load || !variant)))
+        return fail(PIKAMD_EINVAL, "bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize()); // (the routers of the calls in flight write what is read and overwritten here)
+    if (publish_load >= 0) {
+        const uint32_t v = publish_load > 0xffffffffll ? 0xffffffffu : (uint32_t)publish_load;
+        HIP_TRY(hipMemcpy(pik::route_loads(s) + slot, &v, sizeof v, hipMemcpyHostToDevice));
+    }
+    const int routed = ext_of(s)->routed_passes[slot];
+    if (n_passes) *n_passes = routed;
+    if (routed > 0 && max_passes > 0) {
+        uint32_t rec[pik::ROUTE_MAX_PASSES * 4];
+        HIP_TRY(hipMemcpy(rec, pik::route_record(s, slot), sizeof rec, hipMemcpyDeviceToHost));
+        for (int k = 0; k < routed && k < max_passes; ++k) {
+            survivors[k] = rec[4 * k + 0];
+            others_load[k] = rec[4 * k + 1];
+            variant[k] = (int32_t)rec[4 * k + 2];
+        }
+    }
+    return 0;
 }
 
 } // extern "C"

@@ -167,6 +167,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_shard_bounds", "pikamd_solve_batch_sharded", "pikamd_self_test", "pikamd_self_test_cost",
     "pikamd_solve_paths", "pikamd_solve_paths_device", "pikamd_path_kernel_name",
     "pikamd_search_batch", "pikamd_search_batch_device", "pikamd_search_kernel_name",
+    "pikamd_debug_regime",
 )
 
 _libs = {}
@@ -264,6 +265,9 @@ def lib(strict: bool = False):
     L.pikamd_search_batch_device.restype = C.c_int32
     L.pikamd_search_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, ip]
     L.pikamd_search_kernel_name.restype = C.c_char_p
+    up = C.POINTER(C.c_uint32)
+    L.pikamd_debug_regime.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, ip, up, up, ip]
+    L.pikamd_debug_regime.restype = C.c_int32
     for name in ("pikamd_create", "pikamd_variables", "pikamd_fk_batch", "pikamd_cost_batch",
                  "pikamd_gd_step_batch", "pikamd_solve_batch", "pikamd_solve_batch_device",
                  "pikamd_fk_batch_device", "pikamd_solve_batches_device",
@@ -412,10 +416,31 @@ class Solver:
     # ---- scheduling options (pikamd_set_option) -------------------------------------------
     def set_option(self, name: str, value) -> None:
         """Pin one scheduling choice of this handle ("lanes_per_elite", "lanes_per_elite_schedule",
-        "passes", "two_per_simd", "regime", "search_schedule"; None / "" restores the default).  Results never depend on
+        "passes", "two_per_simd", "regime", "device_regime", "regime_threshold", "search_schedule"; None / "" restores
+        the default).  Results never depend on
         these."""
         v = b"" if value is None else str(value).encode()
         self._chk(self._L.pikamd_set_option(self._h, name.encode(), v))
+
+    #: lanes per elite of the kernel variant ids pikamd_debug_regime reports (7: one lane, two wavefronts per SIMD)
+    VARIANT_LANES = {5: 16, 4: 8, 3: 4, 2: 2, 1: 1, 7: 1}
+    MAX_PASSES = 16
+
+    def debug_regime(self, slot: int = 0, publish_load: int = -1):
+        """pikamd_debug_regime (synchronises the device): what the routers of the LAST solve call on `slot` decided --
+        None when that call was not routed (host rule), else a list with one (survivors, others_load, variant id)
+        per pass.  publish_load >= 0 first sets the load `slot` shows the other slots' routers (an artificial load
+        on a slot with no call in flight)."""
+        n = C.c_int32(0)
+        sv = np.zeros(self.MAX_PASSES, dtype=np.uint32)
+        ol = np.zeros(self.MAX_PASSES, dtype=np.uint32)
+        var = np.zeros(self.MAX_PASSES, dtype=np.int32)
+        up = C.POINTER(C.c_uint32)
+        self._chk(self._L.pikamd_debug_regime(self._h, slot, int(publish_load), self.MAX_PASSES, C.byref(n),
+                                              sv.ctypes.data_as(up), ol.ctypes.data_as(up), _ip(var)))
+        if n.value < 0:
+            return None
+        return [(int(sv[k]), int(ol[k]), int(var[k])) for k in range(n.value)]
 
     def self_test(self, params: Params, n: int = 64) -> int:
         """pikamd_self_test: every kernel variant against the one-lane kernel on n generated targets of this
@@ -435,7 +460,8 @@ class Solver:
     ENV_OPTIONS = (("PIK_LPE", "lanes_per_elite"), ("PIK_LPE_SCHED", "lanes_per_elite_schedule"),
                    ("PIK_PASSES", "passes"), ("PIK_OCC2", "two_per_simd"), ("PIK_REGIME", "regime"),
                    ("PIK_SPECIALISED", "specialised"), ("PIK_SHARD_CHUNKS", "shard_chunks"),
-                   ("PIK_SELF_TEST", "self_test"))
+                   ("PIK_SELF_TEST", "self_test"), ("PIK_DEVICE_REGIME", "device_regime"),
+                   ("PIK_REGIME_THRESHOLD", "regime_threshold"))
     # (no environment form of "joint_layout": it changes what the arrays mean, callers set it explicitly)
 
     def _env_options(self) -> None:
