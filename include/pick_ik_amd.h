@@ -523,8 +523,7 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
  * a caller who collision-checks them); row a is what one pikamd_solve_batch from start a returns.  The primary
  * outputs are the loop's whether or not all_* is given.
  * The approximate-solution gate (src/pick_ik_plugin.cpp:219-267) and the solution callback stay with the caller.
- * GLOBAL mode (mode 0) is refused: a restart attempt of the memetic kernels would have to start a first pass from a
- * device-side list of the failed problems, which their launch does not offer.
+ * GLOBAL mode (mode 0) is refused here: pikamd_search_global_batch serves it.
  *   goal_pos_quat [B][n_tips][7], seed [B][dof], initial_guess [B][dof] (NULL = seed), solution [B][dof], status [B],
  *   final_cost [B] (may be NULL), stats [B] (may be NULL), attempts [B] (may be NULL),
  *   all_solution [B][max_attempts][dof] (may be NULL), all_status [B][max_attempts] (may be NULL).
@@ -553,6 +552,58 @@ int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int
  * of every problem on the chip at once, a small finalize kernel behind them) */
 const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t B,
                                       int32_t max_attempts, int32_t* attempts_in_flight);
+/* ---- Memetic IK with random restarts (global mode) -------------------------------------------------
+ * The same loop around the memetic solver, for B problems and up to max_attempts attempts each in ONE call.
+ * p->mode must be 0 (global mode; mode 1 is pikamd_search_batch's).  The result is DEFINED as this loop, bit for bit:
+ *
+ *   init[b] = initial_guess ? initial_guess[b] : seed[b]
+ *   if init[b] is invalid (a bounded variable outside its limits, or a NaN): init[b] = draw(b, 0, init[b])
+ *   for a in 0 .. max_attempts-1, for every b still open:
+ *     (sol, st, cost, stats) = one pikamd_batch record {B = 1, goal[b], seed[b], initial_guess = init[b],
+ *                                problem_offset = problem_offset + b} solved by pikamd_solve_batches in global mode
+ *                                with rng_seed_a = rng_seed + ((uint64_t)a << 32)      (mod 2^64)
+ *     solution[b] = sol; status[b] = st; final_cost[b] = cost; stats[b] += stats (field by field); attempts[b] = a + 1
+ *     if st > 0: b is closed     else: init[b] = draw(b, a + 1, init[b])
+ *
+ * draw is exactly the draw of pikamd_search_batch above: Philox stream RESTART (= 3), keyed by the CALLER's rng_seed
+ * (not rng_seed_a), every operation rounded on its own.
+ * Why a << 32: a draw's key is ((uint32)seed ^ stream, (seed >> 32) + (problem >> 32)).  Adding a to the LOW word
+ * would make attempt 1's REPRODUCE key (stream 2) equal attempt 0's RESTART key -- (0 + 1) ^ 2 == 0 ^ 3.  The high
+ * word gives every attempt INIT / REPRODUCE streams of its own for all problem indices below 2^32; a = 0 is the
+ * caller's seed unchanged.
+ *
+ * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch.  With
+ * return_approximate_solution set, every problem closes at attempt 0.  A batch cut into calls or shards with matching
+ * problem_offset gives the answers of one call.  A restart starts from the re-drawn state, as the plugin shim's loop
+ * does (the reference re-randomises init_state but keeps passing ik_seed_state; seed[b] stays the displacement
+ * reference and what a failure returns).  The approximate-solution gate and the solution callback stay with the
+ * caller.
+ * all_solution [B][max_attempts][dof] / all_status [B][max_attempts]: when either is given EVERY attempt of every
+ * problem runs, without an early exit; row a is what the one-record solve above returns from the start the loop's
+ * draws give attempt a (every attempt counted as failed) with rng_seed_a.  The primary outputs are the loop's either
+ * way.
+ * Accepts what pikamd_solve_batch accepts in global mode: every kernel flavour, species, several tip frames,
+ * floating and mimic chains, unbounded variables.  max_attempts is 1..PIKAMD_MAX_ATTEMPTS; B = 0 returns 0; NULL is
+ * checked as in pikamd_search_batch (final_cost, stats, attempts, all_* may be NULL).  Not with the option
+ * joint_layout = soa.  No completion counters. */
+/* host pointers; synchronous, staged through the library's own pinned buffers and stream, behind the automatic
+ * self test of the GLOBAL-mode kernels.  Stops enqueuing attempts once no problem is open. */
+int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int64_t B, const double* goal_pos_quat,
+                                   const double* seed, const double* initial_guess, uint64_t rng_seed,
+                                   int64_t problem_offset, int32_t max_attempts, double* solution, int32_t* status,
+                                   double* final_cost, pikamd_stats* stats, int32_t* attempts, double* all_solution,
+                                   int32_t* all_status);
+/* device pointers; enqueues ALL max_attempts attempts on `stream` and returns without synchronising, no self test
+ * (see pikamd_solve_batch_device for `slot`): the passes of an attempt nobody is open for find a count of 0 and
+ * return.  The scratch of the call (the starts, one attempt's rows, the open list) belongs to the handle's slot; it
+ * grows only when a call needs more than any earlier call on that slot did (a grow frees, and a free synchronises
+ * the device: run the largest call first where that matters). */
+int32_t pikamd_search_global_batch_device(pikamd_solver* s, const pikamd_params* p, int64_t B,
+                                          const double* d_goal_pos_quat, const double* d_seed,
+                                          const double* d_initial_guess, uint64_t rng_seed, int64_t problem_offset,
+                                          int32_t max_attempts, double* d_solution, int32_t* d_status,
+                                          double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
+                                          double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -7,7 +7,8 @@ joints, and a single translation unit took 2.5 minutes; the seventeen objects bu
 only the ones whose inputs changed are rebuilt.  Objects live in pick_ik_amd/_build/ (git-ignored).
 The waypoint-path kernels (pik_path_inst.hip) are translation units of their own, one per chain length for the
 flavours fast, exact and strict (_path_objects); so are the restart-search kernels (pik_search_inst.hip,
-_search_objects) and the routed launcher (pik_route_inst.hip, _route_objects: the product library's four flavours).
+_search_objects), the routed launcher (pik_route_inst.hip, _route_objects: the product library's four flavours) and
+the restart launcher of global mode (pik_restart_inst.hip, _restart_objects: those four and the strict flavour).
 """
 from __future__ import annotations
 
@@ -26,7 +27,8 @@ LIB = os.path.join(_HERE, "libpick_ik_amd.so")
 # math mode (tests/test_gpu_strict_parity.py).  ~2x slower.
 LIB_STRICT = os.path.join(_HERE, "libpick_ik_amd_strict.so")
 HEADERS = ["pik_kernels.hpp", "pik_math.hpp", "pik_host.hpp", "pik_solver.hpp", "pik_launch.hpp", "pik_exact.hpp",
-           "pik_host_solve.hpp", "pik_path.hpp", "pik_path_ops.hpp", "pik_search.hpp", "pik_search_ops.hpp", "pik_route.hpp", "pik_route_ops.hpp"]
+           "pik_host_solve.hpp", "pik_path.hpp", "pik_path_ops.hpp", "pik_search.hpp", "pik_search_ops.hpp", "pik_route.hpp", "pik_route_ops.hpp",
+           "pik_restart.hpp", "pik_restart_ops.hpp"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pick_ik_amd.h")
 DOFS = tuple(range(1, 17))
 BUILD_DIR = os.path.join(_HERE, "_build")
@@ -138,6 +140,23 @@ def _all_route_objects():
     return [o for fl in ROUTE_FLAVOURS for o in _route_objects(fl)]
 
 
+def _restart_objects(flavour: str):
+    """the per-length objects of the restart launcher of global mode (pik_restart_inst.hip -> pik_restart.hpp) of one
+    flavour: the product library's four and "strict", compiled with the flags of that flavour's pik_inst objects and
+    linked behind the route objects.  They hold the prepare and fold kernels and references to the flavour's memetic
+    kernels, no copy of them."""
+    d = os.path.join(BUILD_DIR, flavour)
+    fl = {"fast": [], "strict": [], "exact": EXACT_FLAGS, "common": COMMON_FLAGS, "common_goals": COMMON_GOALS_FLAGS}[flavour]
+    only = os.environ.get("PIK_ONLY_D")
+    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
+    return [(os.path.join(d, f"pik_restart_inst_d{n}.o"), "pik_restart_inst.hip",
+             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
+
+
+def _all_restart_objects(strict: bool):
+    return _restart_objects("strict") if strict else [o for fl in ROUTE_FLAVOURS for o in _restart_objects(fl)]
+
+
 def _common_objects(goals: bool = False):
     """the per-length objects of the common-configuration flavours (fast flags + -DPIK_COMMON=1 [-DPIK_NO_GOALS=0])"""
     d = os.path.join(BUILD_DIR, "common_goals" if goals else "common")
@@ -243,7 +262,8 @@ def _deps(src, strict_flags: bool):
 
 
 def _sources():
-    return ([os.path.join(CSRC, f) for f in ("pik_amd.hip", "pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip", "pik_urdf.hpp",
+    return ([os.path.join(CSRC, f) for f in ("pik_amd.hip", "pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip",
+                                             "pik_restart_inst.hip", "pik_urdf.hpp",
                                              *HEADERS)] +
             [HEADER, os.path.abspath(__file__)])
 
@@ -252,8 +272,9 @@ def _lib_stamp(strict: bool) -> str:
     """what a library was linked from: flavour flags + the chain lengths with real kernels"""
     flags = _flavor_flags(strict) + ([] if strict else ["+exact:"] + EXACT_FLAGS + ["+common:"] + COMMON_FLAGS + ["+common_goals:"] + COMMON_GOALS_FLAGS)
     # (+paths: the waypoint-path objects are linked in -- a library from before them is not this one)
-    # (+search: ... and the restart-search objects; +route: ... and, in the product library, the routed launcher's)
-    return _stamp(flags + ["+paths", "+search"] + ([] if strict else ["+route"]) + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
+    # (+search: ... and the restart-search objects; +route: ... and, in the product library, the routed launcher's;
+    #  +restart: ... and the restart launcher's)
+    return _stamp(flags + ["+paths", "+search"] + ([] if strict else ["+route"]) + ["+restart"] + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
 
 
 def is_stale(lib: str = LIB) -> bool:
@@ -367,9 +388,11 @@ def ledger_rows():
     rows = []
     for o in (_objects(False) + _exact_objects() + _common_objects() + _common_objects(True) + _objects(True) +
               _path_objects("fast") + _path_objects("exact") + _path_objects("strict") +
-              _search_objects("fast") + _search_objects("exact") + _search_objects("strict") + _all_route_objects()):
+              _search_objects("fast") + _search_objects("exact") + _search_objects("strict") + _all_route_objects() +
+              _all_restart_objects(False) + _all_restart_objects(True)):
         res = o[0] + ".res"
-        if o[1] not in ("pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip"):
+        if o[1] not in ("pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip",
+                        "pik_restart_inst.hip"):
             continue
         if not os.path.exists(res):
             return None
@@ -423,6 +446,8 @@ def build_library(force: bool = False, verbose: bool = False, strict_too: bool =
         # + the routed launcher, behind the search objects (product library only)
         if not strict:
             objs = objs + _all_route_objects()
+        # + the restart launcher of global mode, behind the route objects (both libraries)
+        objs = objs + _all_restart_objects(strict)
         stale = [o for o in objs if force or _obj_stale(*o, _is_strict_obj(o))]
         jobs += [(o, _is_strict_obj(o)) for o in stale if (o, _is_strict_obj(o)) not in jobs]
         relink.append((lib, [o[0] for o in objs]))

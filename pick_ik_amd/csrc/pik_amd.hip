@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pik_path_ops.hpp"
+#include "pik_restart_ops.hpp"
 #include "pik_route_ops.hpp"
 #include "pik_search_ops.hpp"
 #include "pik_solver.hpp"
@@ -69,6 +70,13 @@ PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_F
 PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
 PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
 #undef PIK_FLAVOUR_ROUTE_OPS
+// (... and the restart launcher of global mode, pik_restart_inst.hip: likewise)
+#define PIK_FLAVOUR_RESTART_OPS(N) const void* restart_ops_d##N();
+PIK_FLAVOUR_RESTART_OPS(1) PIK_FLAVOUR_RESTART_OPS(2) PIK_FLAVOUR_RESTART_OPS(3) PIK_FLAVOUR_RESTART_OPS(4)
+PIK_FLAVOUR_RESTART_OPS(5) PIK_FLAVOUR_RESTART_OPS(6) PIK_FLAVOUR_RESTART_OPS(7) PIK_FLAVOUR_RESTART_OPS(8)
+PIK_FLAVOUR_RESTART_OPS(9) PIK_FLAVOUR_RESTART_OPS(10) PIK_FLAVOUR_RESTART_OPS(11) PIK_FLAVOUR_RESTART_OPS(12)
+PIK_FLAVOUR_RESTART_OPS(13) PIK_FLAVOUR_RESTART_OPS(14) PIK_FLAVOUR_RESTART_OPS(15) PIK_FLAVOUR_RESTART_OPS(16)
+#undef PIK_FLAVOUR_RESTART_OPS
 } // namespace pik_exact
 // ... and the kernels specialised for the common configuration (flavour -DPIK_COMMON=1, namespace pik_common;
 // pik_math.hpp says what that is and what it buys)
@@ -85,6 +93,13 @@ PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_F
 PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
 PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
 #undef PIK_FLAVOUR_ROUTE_OPS
+// (... and the restart launcher of global mode, pik_restart_inst.hip: likewise)
+#define PIK_FLAVOUR_RESTART_OPS(N) const void* restart_ops_d##N();
+PIK_FLAVOUR_RESTART_OPS(1) PIK_FLAVOUR_RESTART_OPS(2) PIK_FLAVOUR_RESTART_OPS(3) PIK_FLAVOUR_RESTART_OPS(4)
+PIK_FLAVOUR_RESTART_OPS(5) PIK_FLAVOUR_RESTART_OPS(6) PIK_FLAVOUR_RESTART_OPS(7) PIK_FLAVOUR_RESTART_OPS(8)
+PIK_FLAVOUR_RESTART_OPS(9) PIK_FLAVOUR_RESTART_OPS(10) PIK_FLAVOUR_RESTART_OPS(11) PIK_FLAVOUR_RESTART_OPS(12)
+PIK_FLAVOUR_RESTART_OPS(13) PIK_FLAVOUR_RESTART_OPS(14) PIK_FLAVOUR_RESTART_OPS(15) PIK_FLAVOUR_RESTART_OPS(16)
+#undef PIK_FLAVOUR_RESTART_OPS
 } // namespace pik_common
 // ... and the same with the joint goals left in (-DPIK_NO_GOALS=0): BASELINE config 3's kind of call
 namespace pik_common_goals {
@@ -100,6 +115,13 @@ PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_F
 PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
 PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
 #undef PIK_FLAVOUR_ROUTE_OPS
+// (... and the restart launcher of global mode, pik_restart_inst.hip: likewise)
+#define PIK_FLAVOUR_RESTART_OPS(N) const void* restart_ops_d##N();
+PIK_FLAVOUR_RESTART_OPS(1) PIK_FLAVOUR_RESTART_OPS(2) PIK_FLAVOUR_RESTART_OPS(3) PIK_FLAVOUR_RESTART_OPS(4)
+PIK_FLAVOUR_RESTART_OPS(5) PIK_FLAVOUR_RESTART_OPS(6) PIK_FLAVOUR_RESTART_OPS(7) PIK_FLAVOUR_RESTART_OPS(8)
+PIK_FLAVOUR_RESTART_OPS(9) PIK_FLAVOUR_RESTART_OPS(10) PIK_FLAVOUR_RESTART_OPS(11) PIK_FLAVOUR_RESTART_OPS(12)
+PIK_FLAVOUR_RESTART_OPS(13) PIK_FLAVOUR_RESTART_OPS(14) PIK_FLAVOUR_RESTART_OPS(15) PIK_FLAVOUR_RESTART_OPS(16)
+#undef PIK_FLAVOUR_RESTART_OPS
 } // namespace pik_common_goals
 #endif
 
@@ -118,6 +140,8 @@ struct SolverExt : pikamd_solver {
     int device_regime = 1;
     long long regime_threshold = 0;
     int routed_passes[pik::N_SLOTS];
+    // pikamd_search_global_batch*: per slot the starts, the rows of one attempt, the open flags and the open list
+    pik::DevBuf restart_rows[pik::N_SLOTS];
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -314,6 +338,31 @@ const pik::SearchOps* search_ops_of(const pikamd_solver* s, const pikamd_params*
     return pik::search_ops(s->chain.dof);
 }
 
+// ... and the restart launcher of a global-mode call (pik_restart.hpp), in the flavour solve_ops_of picks
+const pik::RestartOps* restart_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
+#if !defined(PIK_STRICT)
+    const bool common = common_eligible(s, p, pk), goals = pk.goal_mask != 0, literal = needs_literal(s, p);
+    const void* r = nullptr;
+    switch (s->chain.dof) {
+#define PIK_RESTART_CASE(N)                                                                                           \
+    case N:                                                                                                           \
+        r = common ? (goals ? pik_common_goals::restart_ops_d##N() : pik_common::restart_ops_d##N())                  \
+                   : literal ? pik_exact::restart_ops_d##N() : static_cast<const void*>(pik::restart_ops_d##N());     \
+        break;
+        PIK_RESTART_CASE(1) PIK_RESTART_CASE(2) PIK_RESTART_CASE(3) PIK_RESTART_CASE(4) PIK_RESTART_CASE(5)
+        PIK_RESTART_CASE(6) PIK_RESTART_CASE(7) PIK_RESTART_CASE(8) PIK_RESTART_CASE(9) PIK_RESTART_CASE(10)
+        PIK_RESTART_CASE(11) PIK_RESTART_CASE(12) PIK_RESTART_CASE(13) PIK_RESTART_CASE(14) PIK_RESTART_CASE(15)
+        PIK_RESTART_CASE(16)
+#undef PIK_RESTART_CASE
+        default: break;
+    }
+    return static_cast<const pik::RestartOps*>(r);
+#else
+    (void)p, (void)pk;
+    return pik::restart_ops(s->chain.dof);
+#endif
+}
+
 size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 } // namespace
@@ -505,6 +554,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : s->slot_state) b.release();
     for (auto& b : s->slot_soa) b.release();
     for (auto& b : ext_of(s)->search_rows) b.release();
+    for (auto& b : ext_of(s)->restart_rows) b.release();
     for (auto& j : s->jobs) {
         j.dev.release();
         j.host.release();
@@ -1713,6 +1763,213 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
                  s->n_tips > 1 ? "true" : "false");
     return m->kernel_name;
 }
+
+} // extern "C"
+
+// ---- memetic IK with random restarts (pik_restart.hpp) --------------------------------------------
+namespace {
+
+int check_search_global(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t K, bool any_null,
+                        pik::ParamsK& pk) {
+    if (int rc = check_solver(s)) return rc;
+    if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
+    if (p->mode != 0)
+        return fail(PIKAMD_EINVAL,
+                    "pikamd_search_global_batch: restarts of the memetic solver (mode = 0), got mode %d: local mode is "
+                    "served by pikamd_search_batch",
+                    (int)p->mode);
+    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
+        return fail(PIKAMD_EINVAL, "pikamd_search_global_batch: max_attempts %d: expected 1..%d", (int)K, PIKAMD_MAX_ATTEMPTS);
+    if (B < 0) return fail(PIKAMD_EINVAL, "pikamd_search_global_batch: B = %lld: expected B >= 0", (long long)B);
+    if (s->opt.soa)
+        return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_search_global_batch (its arrays are [B][dof])");
+    if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
+    if (B > 0 && any_null)
+        return fail(PIKAMD_EINVAL, "pikamd_search_global_batch: goal_pos_quat, seed, solution and status must not be NULL");
+    return 0;
+}
+
+// The attempts of one call on `stream` (device pointers in `r`: B, K, user_guess, the key, the primary outputs and
+// all_*; goal / seed apart).  sync_between: the host-pointer entry point -- the open count is read back behind every
+// fold, and no attempt is enqueued once it is zero.
+int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pik::RestartOps* ops,
+                      pik::RestartArgs r, const double* d_goal, const double* d_seed, hipStream_t stream, int slot,
+                      bool sync_between) {
+    const size_t n = (size_t)r.B, d = (size_t)s->chain.dof;
+    // the slot's scratch: guess | row solution | row cost | row stats | row status | open | list
+    const size_t off_guess = 0, off_sol = off_guess + sizeof(double) * d * n, off_cost = off_sol + sizeof(double) * d * n;
+    const size_t off_stats = off_cost + sizeof(double) * n, off_status = off_stats + sizeof(pikamd_stats) * n;
+    const size_t off_open = off_status + align8(sizeof(int32_t) * n), off_list = off_open + align8(sizeof(int32_t) * n);
+    const size_t total = off_list + align8(sizeof(int32_t) * n);
+    pik::DevBuf& buf = ext_of(s)->restart_rows[slot];
+    if (int rc = buf.ensure(total)) return rc;
+    if (int rc = ops->reserve(s, p, pk, r.B, slot)) return rc;
+    char* w = (char*)buf.p;
+    unsigned* n_list = (unsigned*)(s->counters + pik::COUNTER_BLOCK * (size_t)slot + 128);
+    r.guess = (double*)(w + off_guess);
+    r.row_solution = (const double*)(w + off_sol);
+    r.row_cost = (const double*)(w + off_cost);
+    r.row_stats = w + off_stats;
+    r.row_status = (const int*)(w + off_status);
+    r.open = (int*)(w + off_open);
+    r.list = (int*)(w + off_list);
+    r.n_list = n_list;
+    r.every = (r.all_solution || r.all_status) ? 1 : 0;
+    pik::BatchRecord rec;
+    std::memset(&rec, 0, sizeof rec);
+    rec.B = r.B;
+    rec.goal = d_goal;
+    rec.seed = d_seed;
+    rec.guess = r.guess;
+    rec.problem_offset = r.problem_offset;
+    rec.solution = (double*)(w + off_sol);
+    rec.status = (int*)(w + off_status);
+    rec.cost = (double*)(w + off_cost);
+    rec.stats = w + off_stats;
+    // (a launch that failed half-way leaves counters behind: the next call on the slot clears them)
+    auto give_up = [&](int rc) {
+        s->counters_dirty[slot] = true;
+        return rc;
+    };
+    if (s->counters_dirty[slot]) {
+        HIP_TRY(hipMemsetAsync(s->counters + pik::COUNTER_BLOCK * (size_t)slot, 0, pik::COUNTER_BLOCK, stream));
+        s->counters_dirty[slot] = false;
+    }
+    if (int rc = ops->prepare(s, pk, r, stream, slot)) return rc;
+    long long open = r.B;
+    for (int a = 0; a < r.K; ++a) {
+        const unsigned long long seed_a = pik::restart_attempt_seed(r.rng_seed, a);
+        if (a == 0) {
+            if (int rc = run_solve(s, p, pk, &rec, 1, seed_a, stream, slot)) return give_up(rc);
+        } else {
+            pik::BatchRecord copy = rec; // (the launch fills in `start`)
+            if (int rc = ops->attempt(s, p, pk, &copy, seed_a, r.list, sync_between ? open : -1, stream, slot))
+                return give_up(rc);
+        }
+        r.attempt = a;
+        r.last = (a == r.K - 1) ? 1 : 0;
+        if (int rc = ops->fold(s, pk, r, stream, slot)) return give_up(rc);
+        if (sync_between && !r.last) {
+            unsigned cnt = 0;
+            hipError_t e = hipMemcpyAsync(&cnt, n_list, sizeof cnt, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return give_up(fail(PIKAMD_EHIP, "pikamd_search_global_batch: %s", hipGetErrorString(e)));
+            open = (long long)cnt;
+            if (open == 0) break;
+        }
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_search_global_batch_device(pikamd_solver* s, const pikamd_params* p, int64_t B,
+                                          const double* d_goal_pos_quat, const double* d_seed,
+                                          const double* d_initial_guess, uint64_t rng_seed, int64_t problem_offset,
+                                          int32_t max_attempts, double* d_solution, int32_t* d_status,
+                                          double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
+                                          double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot) {
+    pik::ParamsK pk;
+    if (int rc = check_search_global(s, p, B, max_attempts, !d_goal_pos_quat || !d_seed || !d_solution || !d_status, pk))
+        return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (B == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    const pik::RestartOps* ops = restart_ops_of(s, p, pk);
+    if (!ops) return no_kernels(s->chain.dof);
+    HIP_TRY(hipSetDevice(s->device));
+    pik::RestartArgs r = {};
+    r.B = B;
+    r.K = max_attempts;
+    r.user_guess = d_initial_guess ? d_initial_guess : d_seed;
+    r.rng_seed = rng_seed;
+    r.problem_offset = problem_offset;
+    r.solution = d_solution;
+    r.status = d_status;
+    r.cost = d_final_cost;
+    r.stats = d_stats;
+    r.attempts = d_attempts;
+    r.all_solution = d_all_solution;
+    r.all_status = d_all_status;
+    return run_search_global(s, p, pk, ops, r, d_goal_pos_quat, d_seed, (hipStream_t)stream, slot, false);
+}
+
+int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int64_t B, const double* goal_pos_quat,
+                                   const double* seed, const double* initial_guess, uint64_t rng_seed,
+                                   int64_t problem_offset, int32_t max_attempts, double* solution, int32_t* status,
+                                   double* final_cost, pikamd_stats* stats, int32_t* attempts, double* all_solution,
+                                   int32_t* all_status) {
+    pik::ParamsK pk;
+    if (int rc = check_search_global(s, p, B, max_attempts, !goal_pos_quat || !seed || !solution || !status, pk)) return rc;
+    if (B == 0) return 0;
+    if (int rc = maybe_self_test(s, p)) return rc; // (the GLOBAL-mode kernel set, as pikamd_solve_batch)
+    const pik::RestartOps* ops = restart_ops_of(s, p, pk);
+    if (!ops) return no_kernels(s->chain.dof);
+    // staged like pikamd_search_batch, through the synchronous entry points' job
+    const int job = PIKAMD_MAX_HOST_JOBS - 1;
+    pik::HostJob& J = s->jobs[job];
+    if (J.pending) return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", job);
+    HIP_TRY(hipSetDevice(s->device));
+    if (!J.stream) HIP_TRY(hipStreamCreateWithFlags(&J.stream, hipStreamNonBlocking));
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, n = (size_t)B, rows = n * (size_t)max_attempts;
+    const size_t off_goal = 0, off_seed = off_goal + sizeof(double) * g7 * n, off_guess = off_seed + sizeof(double) * d * n;
+    const size_t in_bytes = off_guess + (initial_guess ? sizeof(double) * d * n : 0);
+    const size_t off_solution = in_bytes, off_cost = off_solution + sizeof(double) * d * n;
+    const size_t off_stats = off_cost + sizeof(double) * n, off_status = off_stats + sizeof(pikamd_stats) * n;
+    const size_t off_attempts = off_status + align8(sizeof(int32_t) * n);
+    const size_t off_all_solution = off_attempts + align8(sizeof(int32_t) * n);
+    const size_t off_all_status = off_all_solution + (all_solution ? sizeof(double) * d * rows : 0);
+    const size_t total = off_all_status + (all_status ? align8(sizeof(int32_t) * rows) : 0);
+    if (int rc = J.dev.ensure(total)) return rc;
+    if (int rc = J.host.ensure(total)) return rc;
+    char* hb = (char*)J.host.p;
+    char* db = (char*)J.dev.p;
+    pik::RestartArgs r = {};
+    r.B = B;
+    r.K = max_attempts;
+    r.user_guess = initial_guess ? (const double*)(db + off_guess) : (const double*)(db + off_seed);
+    r.rng_seed = rng_seed;
+    r.problem_offset = problem_offset;
+    r.solution = (double*)(db + off_solution);
+    r.status = (int*)(db + off_status);
+    r.cost = (double*)(db + off_cost);
+    r.stats = (void*)(db + off_stats);
+    r.attempts = (int*)(db + off_attempts);
+    r.all_solution = all_solution ? (double*)(db + off_all_solution) : nullptr;
+    r.all_status = all_status ? (int32_t*)(db + off_all_status) : nullptr;
+    const int slot = pik::N_DEVICE_SLOTS + job;
+    std::memcpy(hb + off_goal, goal_pos_quat, sizeof(double) * g7 * n);
+    std::memcpy(hb + off_seed, seed, sizeof(double) * d * n);
+    if (initial_guess) std::memcpy(hb + off_guess, initial_guess, sizeof(double) * d * n);
+    HIP_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, J.stream));
+    // (work of this call may be in flight from here on: the stream is drained before an error is returned)
+    if (int rc = run_search_global(s, p, pk, ops, r, (const double*)(db + off_goal), (const double*)(db + off_seed),
+                                   J.stream, slot, true)) {
+        (void)hipStreamSynchronize(J.stream);
+        return rc;
+    }
+    {
+        hipError_t e = hipMemcpyAsync(hb + in_bytes, db + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, J.stream);
+        const hipError_t e2 = hipStreamSynchronize(J.stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess)
+            return fail(PIKAMD_EHIP, "pikamd_search_global_batch: %s (its results are lost)", hipGetErrorString(e));
+    }
+    std::memcpy(solution, hb + off_solution, sizeof(double) * d * n);
+    std::memcpy(status, hb + off_status, sizeof(int32_t) * n);
+    if (final_cost) std::memcpy(final_cost, hb + off_cost, sizeof(double) * n);
+    if (stats) std::memcpy(stats, hb + off_stats, sizeof(pikamd_stats) * n);
+    if (attempts) std::memcpy(attempts, hb + off_attempts, sizeof(int32_t) * n);
+    if (all_solution) std::memcpy(all_solution, hb + off_all_solution, sizeof(double) * d * rows);
+    if (all_status) std::memcpy(all_status, hb + off_all_status, sizeof(int32_t) * rows);
+    return 0;
+}
+
+} // extern "C"
+
+extern "C" {
 
 // ---- the routed launcher's record (tests, profile scripts) ----------------------------------------
 

@@ -157,7 +157,7 @@ struct PathResult {
     std::vector<int32_t> reached; // [P] leading held waypoints: reached / W is computeCartesianPath's fraction
 };
 
-// Solver::ik_gradient_search_batch: local mode with random restarts
+// Solver::ik_gradient_search_batch: local mode with random restarts (ik_memetic_search_batch: global mode)
 struct SearchResult {
     BatchResult batch;                 // what the loop of restarts returned per problem (stats summed over its attempts)
     std::vector<int32_t> attempts;     // [B] attempts made: the winner's index + 1, max_attempts when none succeeded
@@ -488,6 +488,49 @@ class Solver {
                                 max_attempts, r.batch.solution.data(), r.batch.status.data(), r.batch.cost.data(),
                                 r.batch.stats.data(), r.attempts.data(), all_attempts ? r.all_solution.data() : nullptr,
                                 all_attempts ? r.all_status.data() : nullptr) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return r;
+    }
+
+    // Global mode with random restarts (pikamd_search_global_batch): the same loop around ik_memetic.  Attempt a
+    // solves with rng_seed + (a << 32); the restart states are keyed by (rng_seed, problem_offset + b, attempt) as in
+    // ik_gradient_search_batch.  all_attempts: every attempt of every problem is run and recorded.
+    SearchResult ik_memetic_search_batch(const std::vector<double>& seeds, const std::vector<Pose>& goals,
+                                         const CostSpec& costs, const MemeticIkParams& params, int max_attempts,
+                                         uint64_t rng_seed = 0, int64_t problem_offset = 0,
+                                         bool approx_solution = false, bool all_attempts = false,
+                                         const std::vector<double>* initial_guesses = nullptr) const {
+        if (max_attempts < 1 || max_attempts > PIKAMD_MAX_ATTEMPTS)
+            throw std::invalid_argument("pick_ik_amd: max_attempts outside 1 .. PIKAMD_MAX_ATTEMPTS");
+        if (goals.size() % static_cast<size_t>(n_tips_) != 0)
+            throw std::invalid_argument("pick_ik_amd: goals size is not a multiple of n_tips");
+        const size_t B = goals.size() / static_cast<size_t>(n_tips_), rows = B * static_cast<size_t>(max_attempts);
+        if (seeds.size() != B * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: seeds size != B * dof");
+        if (initial_guesses && initial_guesses->size() != seeds.size())
+            throw std::invalid_argument("pick_ik_amd: initial_guesses size != B * dof");
+        const pikamd_params p = to_params(costs, &params, nullptr, approx_solution);
+        std::vector<double> g7(7 * goals.size());
+        for (size_t b = 0; b < goals.size(); ++b) {
+            const Pose& g = goals[b];
+            const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+            for (int k = 0; k < 7; ++k) g7[7 * b + k] = v[k];
+        }
+        SearchResult r;
+        r.batch.solution.resize(B * dof_);
+        r.batch.status.resize(B);
+        r.batch.cost.resize(B);
+        r.batch.stats.resize(B);
+        r.attempts.resize(B);
+        if (all_attempts) {
+            r.all_solution.resize(rows * dof_);
+            r.all_status.resize(rows);
+        }
+        if (pikamd_search_global_batch(h_, &p, static_cast<int64_t>(B), g7.data(), seeds.data(),
+                                       initial_guesses ? initial_guesses->data() : nullptr, rng_seed, problem_offset,
+                                       max_attempts, r.batch.solution.data(), r.batch.status.data(),
+                                       r.batch.cost.data(), r.batch.stats.data(), r.attempts.data(),
+                                       all_attempts ? r.all_solution.data() : nullptr,
+                                       all_attempts ? r.all_status.data() : nullptr) != 0)
             throw std::runtime_error(pikamd_last_error());
         return r;
     }
