@@ -1,14 +1,12 @@
 """Builds pick_ik_amd/libpick_ik_amd.so (+ the strict verification build) from csrc/ with hipcc for
 gfx950, in-tree so that the .so travels with the repository snapshot to the GPU box.
 
-The library is one translation unit for the C ABI (pik_amd.hip) plus one per supported chain length
-(pik_inst.hip compiled with -DPIK_INST_D=1..16): the kernels are templates over the number of
-joints, and a single translation unit took 2.5 minutes; the seventeen objects build in parallel and
-only the ones whose inputs changed are rebuilt.  Objects live in pick_ik_amd/_build/ (git-ignored).
-The waypoint-path kernels (pik_path_inst.hip) are translation units of their own, one per chain length for the
-flavours fast, exact and strict (_path_objects); so are the restart-search kernels (pik_search_inst.hip,
-_search_objects), the routed launcher (pik_route_inst.hip, _route_objects: the product library's four flavours) and
-the restart launcher of global mode (pik_restart_inst.hip, _restart_objects: those four and the strict flavour).
+A library is the C ABI translation unit (pik_amd.hip), the host solver (pik_host_solve.hip) and, per kernel FAMILY
+and FLAVOUR, one object per supported chain length: the kernels are templates over the number of joints, a single
+translation unit took 2.5 minutes, and the per-length objects build in parallel, only those whose inputs changed.
+Two tables say what there is -- FLAVOURS (build directory -> kernel namespace and flags) and FAMILIES (source file ->
+the flavours it is built for in each library) --, family_objects() expands one (family, flavour) over the lengths and
+library_objects() is the link list, in link order.  Objects live in pick_ik_amd/_build/ (git-ignored).
 """
 from __future__ import annotations
 
@@ -26,9 +24,6 @@ LIB = os.path.join(_HERE, "libpick_ik_amd.so")
 # arithmetic in the reference's operation order, bit-comparable with the CPU oracle's portable
 # math mode (tests/test_gpu_strict_parity.py).  ~2x slower.
 LIB_STRICT = os.path.join(_HERE, "libpick_ik_amd_strict.so")
-HEADERS = ["pik_kernels.hpp", "pik_math.hpp", "pik_host.hpp", "pik_solver.hpp", "pik_launch.hpp", "pik_exact.hpp",
-           "pik_host_solve.hpp", "pik_path.hpp", "pik_path_ops.hpp", "pik_search.hpp", "pik_search_ops.hpp", "pik_route.hpp", "pik_route_ops.hpp",
-           "pik_restart.hpp", "pik_restart_ops.hpp"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pick_ik_amd.h")
 DOFS = tuple(range(1, 17))
 BUILD_DIR = os.path.join(_HERE, "_build")
@@ -41,130 +36,77 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-COMMON_FLAGS = ["-DPIK_COMMON=1"]  # third flavour: the kernels specialised for the common configuration (pik_math.hpp)
-# ... and the same with the joint goals left in (center / avoid-limits / minimal-displacement weights)
-COMMON_GOALS_FLAGS = ["-DPIK_COMMON=1", "-DPIK_NO_GOALS=0"]
-
-
-def _flavor_flags(strict: bool):
+def _base_flags(strict: bool):
     # product build: -ffp-contract=on, i.e. a * b + c is fused where the SOURCE writes it as one
     # expression and nowhere else.  hipcc's default (fast) lets the backend fuse across statements
     # depending on the surrounding code, so the same inlined function could round differently in two
     # kernel variants (seen when the one-lane kernel gained a second evaluation path: its pose cost
     # was contracted differently from the 2..16-lane kernels').  1-2 % slower than fast, and the
     # bit-identity of the variants holds by construction instead of by luck.
-    flags = ["-DPIK_STRICT=1", "-ffp-contract=off"] if strict else ["-ffp-contract=on"]
-    return flags + os.environ.get("PIK_EXTRA_HIPCC_FLAGS", "").split()  # (experiments only)
+    return ["-DPIK_STRICT=1", "-ffp-contract=off"] if strict else ["-ffp-contract=on"]
 
 
-def _objects(strict: bool):
-    """(object path, source, extra flags) of every translation unit of one flavor"""
-    d = os.path.join(BUILD_DIR, "strict" if strict else "fast")
-    only = os.environ.get("PIK_ONLY_D")  # experiments: kernels for these chain lengths only, e.g. "6,7"
-    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    objs = [(os.path.join(d, "pik_amd.o"), "pik_amd.hip", [])]
-    # the host solver for queries with a host cost function: an exact flavour's arithmetic for the host
-    # (product library: the fused one, pik_exact_host_solve; verification library: its own, pik_strict_host_solve)
-    objs.append((os.path.join(d, "pik_host_solve.o"), "pik_host_solve.hip",
-                 ["--cuda-host-only"] + ([] if strict else EXACT_FLAGS)))
-    for n in DOFS:
-        extra = [f"-DPIK_INST_D={n}"] + ([] if n in keep else ["-DPIK_INST_STUB=1"])
-        objs.append((os.path.join(d, f"pik_inst_d{n}.o"), "pik_inst.hip", extra))
-    return objs
-
-
-def _is_strict_obj(o) -> bool:
-    return os.sep + "strict" + os.sep in o[0]
+def _flavor_flags(strict: bool):
+    return _base_flags(strict) + os.environ.get("PIK_EXTRA_HIPCC_FLAGS", "").split()  # (experiments only)
 
 
 # the exact flavour with fused multiply-adds at stated places (pik_math.hpp PIK_XF, namespace pik_exact): the
 # literal kernels the PRODUCT library links (option arithmetic = exact; chains with a floating joint)
 EXACT_FLAGS = ["-DPIK_STRICT=1", "-DPIK_EXACT_FMA=1", "-ffp-contract=off"]
+COMMON_FLAGS = ["-DPIK_COMMON=1"]  # the kernels specialised for the common configuration (pik_math.hpp)
+# ... and the same with the joint goals left in (center / avoid-limits / minimal-displacement weights)
+COMMON_GOALS_FLAGS = ["-DPIK_COMMON=1", "-DPIK_NO_GOALS=0"]
 
-
-def _exact_objects():
-    d = os.path.join(BUILD_DIR, "exact")
-    only = os.environ.get("PIK_ONLY_D")
-    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    return [(os.path.join(d, f"pik_inst_d{n}.o"), "pik_inst.hip",
-             [f"-DPIK_INST_D={n}"] + (EXACT_FLAGS if n in keep else ["-DPIK_INST_STUB=1"] + EXACT_FLAGS)) for n in DOFS]
-
-
-def _is_exact_obj(o) -> bool:
-    return os.sep + "exact" + os.sep in o[0]
-
-
-def _path_objects(flavour: str):
-    """the per-length objects of the waypoint-path kernels (pik_path_inst.hip -> pik_path.hpp) of one flavour: "fast",
-    "exact" or "strict".  Translation units of their own, linked behind everything else: the objects of pik_inst.hip are
-    compiled from the same text and linked in the same order with or without them.  The common-configuration
-    flavours have none (they return the general kernels' bits; pik_amd.hip path_ops_of routes their calls there)."""
-    d = os.path.join(BUILD_DIR, flavour)
-    fl = EXACT_FLAGS if flavour == "exact" else []
-    only = os.environ.get("PIK_ONLY_D")
-    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    return [(os.path.join(d, f"pik_path_inst_d{n}.o"), "pik_path_inst.hip",
-             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
-
-
-def _search_objects(flavour: str):
-    """the per-length objects of the restart-search kernels (pik_search_inst.hip -> pik_search.hpp) of one flavour, as
-    _path_objects; linked behind the path objects"""
-    d = os.path.join(BUILD_DIR, flavour)
-    fl = EXACT_FLAGS if flavour == "exact" else []
-    only = os.environ.get("PIK_ONLY_D")
-    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    return [(os.path.join(d, f"pik_search_inst_d{n}.o"), "pik_search_inst.hip",
-             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
-
-
-#: the flavours of the product library the routed launcher is built for (their memetic kernels are the pik_inst
-#: objects': pik_route_inst.hip only declares them)
+#: flavour = its directory under _build/ -> (the namespace its kernels carry, what pikamd_kernel_name reports in front
+#: of "::"; the flags its per-length objects get behind the library's own).  "strict" is the verification library's
+#: one flavour, the others are the product library's.
+FLAVOURS = {
+    "fast": ("pik", []),
+    "exact": ("pik_exact", EXACT_FLAGS),
+    "common": ("pik_common", COMMON_FLAGS),
+    "common_goals": ("pik_common_goals", COMMON_GOALS_FLAGS),
+    "strict": ("pik_strict", []),
+}
+#: the flavours of the product library: the routed and the restart launcher are built for each of them, with the flags
+#: of the flavour's pik_inst objects (they hold references to its memetic kernels, no copy of them)
 ROUTE_FLAVOURS = ("fast", "exact", "common", "common_goals")
+#: family = its source file -> the flavours it is built for in (the product library, the verification library), in link
+#: order.  The waypoint-path and restart-search kernels have no common-configuration flavours (those return the general
+#: kernels' bits; pik_amd.hip serves their calls with the general ones); the verification library has no routed launcher.
+FAMILIES = {
+    "pik_inst.hip": (ROUTE_FLAVOURS, ("strict",)),
+    "pik_path_inst.hip": (("fast", "exact"), ("strict",)),
+    "pik_search_inst.hip": (("fast", "exact"), ("strict",)),
+    "pik_route_inst.hip": (ROUTE_FLAVOURS, ()),
+    "pik_restart_inst.hip": (ROUTE_FLAVOURS, ("strict",)),
+}
 
 
-def _route_objects(flavour: str):
-    """the per-length objects of the routed launcher (pik_route_inst.hip -> pik_route.hpp) of one flavour of the product
-    library ("fast", "exact", "common", "common_goals"), compiled with the flags of that flavour's pik_inst objects and
-    linked behind the search objects.  They hold the router kernel and references to the flavour's memetic kernels,
-    no copy of them."""
-    d = os.path.join(BUILD_DIR, flavour)
-    fl = {"fast": [], "exact": EXACT_FLAGS, "common": COMMON_FLAGS, "common_goals": COMMON_GOALS_FLAGS}[flavour]
+def family_objects(family: str, flavour: str):
+    """(object path, source, extra flags) of the per-length objects of one family in one flavour.  PIK_ONLY_D
+    (experiments): kernels for these chain lengths only, e.g. "6,7" -- the other lengths are built as stubs."""
     only = os.environ.get("PIK_ONLY_D")
     keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    return [(os.path.join(d, f"pik_route_inst_d{n}.o"), "pik_route_inst.hip",
-             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
+    stem = os.path.join(BUILD_DIR, flavour, os.path.splitext(family)[0])
+    return [(f"{stem}_d{n}.o", family,
+             [f"-DPIK_INST_D={n}"] + ([] if n in keep else ["-DPIK_INST_STUB=1"]) + FLAVOURS[flavour][1]) for n in DOFS]
 
 
-def _all_route_objects():
-    return [o for fl in ROUTE_FLAVOURS for o in _route_objects(fl)]
+def library_objects(strict: bool):
+    """(object path, source, extra flags) of every translation unit of one library, in link order"""
+    d = os.path.join(BUILD_DIR, "strict" if strict else "fast")
+    objs = [(os.path.join(d, "pik_amd.o"), "pik_amd.hip", []),
+            # the host solver for queries with a host cost function: an exact flavour's arithmetic for the host
+            # (product library: the fused one, pik_exact_host_solve; verification library: its own, pik_strict_host_solve)
+            (os.path.join(d, "pik_host_solve.o"), "pik_host_solve.hip", ["--cuda-host-only"] + ([] if strict else EXACT_FLAGS))]
+    for family, flavours in FAMILIES.items():
+        for flavour in flavours[1 if strict else 0]:
+            objs += family_objects(family, flavour)
+    return objs
 
 
-def _restart_objects(flavour: str):
-    """the per-length objects of the restart launcher of global mode (pik_restart_inst.hip -> pik_restart.hpp) of one
-    flavour: the product library's four and "strict", compiled with the flags of that flavour's pik_inst objects and
-    linked behind the route objects.  They hold the prepare and fold kernels and references to the flavour's memetic
-    kernels, no copy of them."""
-    d = os.path.join(BUILD_DIR, flavour)
-    fl = {"fast": [], "strict": [], "exact": EXACT_FLAGS, "common": COMMON_FLAGS, "common_goals": COMMON_GOALS_FLAGS}[flavour]
-    only = os.environ.get("PIK_ONLY_D")
-    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    return [(os.path.join(d, f"pik_restart_inst_d{n}.o"), "pik_restart_inst.hip",
-             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
-
-
-def _all_restart_objects(strict: bool):
-    return _restart_objects("strict") if strict else [o for fl in ROUTE_FLAVOURS for o in _restart_objects(fl)]
-
-
-def _common_objects(goals: bool = False):
-    """the per-length objects of the common-configuration flavours (fast flags + -DPIK_COMMON=1 [-DPIK_NO_GOALS=0])"""
-    d = os.path.join(BUILD_DIR, "common_goals" if goals else "common")
-    fl = COMMON_GOALS_FLAGS if goals else COMMON_FLAGS
-    only = os.environ.get("PIK_ONLY_D")
-    keep = {int(x) for x in only.split(",")} if only else set(DOFS)
-    return [(os.path.join(d, f"pik_inst_d{n}.o"), "pik_inst.hip",
-             [f"-DPIK_INST_D={n}"] + (fl if n in keep else ["-DPIK_INST_STUB=1"] + fl)) for n in DOFS]
+def _is_strict_obj(o) -> bool:
+    return os.sep + "strict" + os.sep in o[0]
 
 
 def _cmd(obj, src, extra, strict):
@@ -262,10 +204,11 @@ def _deps(src, strict_flags: bool):
 
 
 def _sources():
-    return ([os.path.join(CSRC, f) for f in ("pik_amd.hip", "pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip",
-                                             "pik_restart_inst.hip", "pik_urdf.hpp",
-                                             *HEADERS)] +
-            [HEADER, os.path.abspath(__file__)])
+    """every file a library is built from: what its translation units include (_deps), and this file"""
+    seen = []
+    for src in ("pik_amd.hip", "pik_host_solve.hip", *FAMILIES):
+        seen += [f for f in _deps(src, True) if f not in seen]
+    return seen + [os.path.abspath(__file__)]
 
 
 def _lib_stamp(strict: bool) -> str:
@@ -315,14 +258,8 @@ def _link(lib, objs, verbose):
     os.replace(lib + ".tmp", lib)
 
 
-#: kernel namespace (what pikamd_kernel_name reports in front of "::") -> the flags of that flavour's objects
-FLAVOUR_FLAGS = {
-    "pik": ["-ffp-contract=on"],
-    "pik_common": ["-ffp-contract=on"] + COMMON_FLAGS,
-    "pik_common_goals": ["-ffp-contract=on"] + COMMON_GOALS_FLAGS,
-    "pik_exact": EXACT_FLAGS,
-    "pik_strict": ["-DPIK_STRICT=1", "-ffp-contract=off"],
-}
+#: kernel namespace -> the flags of that flavour's pik_inst objects (the exact objects carry their whole flavour, see _cmd)
+FLAVOUR_FLAGS = {ns: (fl if "-DPIK_EXACT_FMA=1" in fl else _base_flags(d == "strict") + fl) for d, (ns, fl) in FLAVOURS.items()}
 _flavour_sha_cache = {}
 
 
@@ -386,13 +323,9 @@ def ledger_rows():
     compiler's resource remarks kept beside the objects; None when an object has none (not built here)"""
     from . import kernel_resources as KR
     rows = []
-    for o in (_objects(False) + _exact_objects() + _common_objects() + _common_objects(True) + _objects(True) +
-              _path_objects("fast") + _path_objects("exact") + _path_objects("strict") +
-              _search_objects("fast") + _search_objects("exact") + _search_objects("strict") + _all_route_objects() +
-              _all_restart_objects(False) + _all_restart_objects(True)):
+    for o in library_objects(False) + library_objects(True):
         res = o[0] + ".res"
-        if o[1] not in ("pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip",
-                        "pik_restart_inst.hip"):
+        if o[1] not in FAMILIES:
             continue
         if not os.path.exists(res):
             return None
@@ -436,18 +369,7 @@ def build_library(force: bool = False, verbose: bool = False, strict_too: bool =
     for lib, strict in flavors:
         if not (force or is_stale(lib) or os.environ.get("PIK_ONLY_D") or os.environ.get("PIK_EXTRA_HIPCC_FLAGS")):
             continue
-        objs = _objects(strict)
-        if not strict:  # + the exact kernels + the common-configuration kernels
-            objs = objs + _exact_objects() + _common_objects() + _common_objects(True)
-        # + the waypoint-path kernels, behind everything that was there before them
-        objs = objs + (_path_objects("strict") if strict else _path_objects("fast") + _path_objects("exact"))
-        # + the restart-search kernels, behind the path objects
-        objs = objs + (_search_objects("strict") if strict else _search_objects("fast") + _search_objects("exact"))
-        # + the routed launcher, behind the search objects (product library only)
-        if not strict:
-            objs = objs + _all_route_objects()
-        # + the restart launcher of global mode, behind the route objects (both libraries)
-        objs = objs + _all_restart_objects(strict)
+        objs = library_objects(strict)
         stale = [o for o in objs if force or _obj_stale(*o, _is_strict_obj(o))]
         jobs += [(o, _is_strict_obj(o)) for o in stale if (o, _is_strict_obj(o)) not in jobs]
         relink.append((lib, [o[0] for o in objs]))

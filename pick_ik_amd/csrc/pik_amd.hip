@@ -33,99 +33,54 @@ char* error_buffer() {
 using pik::fail;
 
 #if !defined(PIK_STRICT)
-// The EXACT kernels inside the product library: the per-length objects of the exact flavour with fused
-// multiply-adds (-DPIK_STRICT -DPIK_EXACT_FMA, namespace pik_exact: MoveIt's chain product, the literal 2 dof + 3
-// cost evaluations per gradient step with the accept evaluation's work re-used, IEEE square roots and divisions
-// -- bit-identical to the oracle's math mode "fma") are linked in as well.  They solve the chains the
-// Denavit-Hartenberg kernels cannot express (a floating joint) and every call of a handle whose option
-// `arithmetic` is `exact`.  All flavours are compiled from the same headers, so the handle, parameter and
-// batch-record layouts are the same types under several namespace names; the launch tables are reached through
-// their mangled names.
+// All flavours are compiled from the same headers, so the handle, parameter and batch-record layouts -- and the ops
+// tables -- are the same types under several namespace names; the tables of the other namespaces are declared
+// `const void*` here (PIK_DECLARE_OPS_FAMILY with the type void) and reached through their mangled names.  The
+// waypoint-path and restart-search kernels are built for the general and the exact flavour only: the kernels of the
+// common configuration return the general ones' bits, a path or search call of theirs is served by the general ones.
 namespace pik_exact {
 char* error_buffer() { return ::pik::error_buffer(); }
-#define PIK_LITERAL_OPS(N) const void* launch_ops_d##N();
-PIK_LITERAL_OPS(1) PIK_LITERAL_OPS(2) PIK_LITERAL_OPS(3) PIK_LITERAL_OPS(4) PIK_LITERAL_OPS(5) PIK_LITERAL_OPS(6)
-PIK_LITERAL_OPS(7) PIK_LITERAL_OPS(8) PIK_LITERAL_OPS(9) PIK_LITERAL_OPS(10) PIK_LITERAL_OPS(11) PIK_LITERAL_OPS(12)
-PIK_LITERAL_OPS(13) PIK_LITERAL_OPS(14) PIK_LITERAL_OPS(15) PIK_LITERAL_OPS(16)
-#undef PIK_LITERAL_OPS
-// (the waypoint-path kernels, pik_path_inst.hip: built for this flavour and the general one -- the kernels of the
-//  common configuration return the general ones' bits, a path call of theirs is served by the general ones)
-#define PIK_LITERAL_PATH_OPS(N) const void* path_ops_d##N();
-PIK_LITERAL_PATH_OPS(1) PIK_LITERAL_PATH_OPS(2) PIK_LITERAL_PATH_OPS(3) PIK_LITERAL_PATH_OPS(4)
-PIK_LITERAL_PATH_OPS(5) PIK_LITERAL_PATH_OPS(6) PIK_LITERAL_PATH_OPS(7) PIK_LITERAL_PATH_OPS(8)
-PIK_LITERAL_PATH_OPS(9) PIK_LITERAL_PATH_OPS(10) PIK_LITERAL_PATH_OPS(11) PIK_LITERAL_PATH_OPS(12)
-PIK_LITERAL_PATH_OPS(13) PIK_LITERAL_PATH_OPS(14) PIK_LITERAL_PATH_OPS(15) PIK_LITERAL_PATH_OPS(16)
-#undef PIK_LITERAL_PATH_OPS
-// (... and the restart-search kernels, pik_search_inst.hip: likewise)
-#define PIK_LITERAL_SEARCH_OPS(N) const void* search_ops_d##N();
-PIK_LITERAL_SEARCH_OPS(1) PIK_LITERAL_SEARCH_OPS(2) PIK_LITERAL_SEARCH_OPS(3) PIK_LITERAL_SEARCH_OPS(4)
-PIK_LITERAL_SEARCH_OPS(5) PIK_LITERAL_SEARCH_OPS(6) PIK_LITERAL_SEARCH_OPS(7) PIK_LITERAL_SEARCH_OPS(8)
-PIK_LITERAL_SEARCH_OPS(9) PIK_LITERAL_SEARCH_OPS(10) PIK_LITERAL_SEARCH_OPS(11) PIK_LITERAL_SEARCH_OPS(12)
-PIK_LITERAL_SEARCH_OPS(13) PIK_LITERAL_SEARCH_OPS(14) PIK_LITERAL_SEARCH_OPS(15) PIK_LITERAL_SEARCH_OPS(16)
-#undef PIK_LITERAL_SEARCH_OPS
-// (... and the routed launcher, pik_route_inst.hip: built for every flavour of the product library)
-#define PIK_FLAVOUR_ROUTE_OPS(N) const void* route_ops_d##N();
-PIK_FLAVOUR_ROUTE_OPS(1) PIK_FLAVOUR_ROUTE_OPS(2) PIK_FLAVOUR_ROUTE_OPS(3) PIK_FLAVOUR_ROUTE_OPS(4)
-PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_FLAVOUR_ROUTE_OPS(8)
-PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
-PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
-#undef PIK_FLAVOUR_ROUTE_OPS
-// (... and the restart launcher of global mode, pik_restart_inst.hip: likewise)
-#define PIK_FLAVOUR_RESTART_OPS(N) const void* restart_ops_d##N();
-PIK_FLAVOUR_RESTART_OPS(1) PIK_FLAVOUR_RESTART_OPS(2) PIK_FLAVOUR_RESTART_OPS(3) PIK_FLAVOUR_RESTART_OPS(4)
-PIK_FLAVOUR_RESTART_OPS(5) PIK_FLAVOUR_RESTART_OPS(6) PIK_FLAVOUR_RESTART_OPS(7) PIK_FLAVOUR_RESTART_OPS(8)
-PIK_FLAVOUR_RESTART_OPS(9) PIK_FLAVOUR_RESTART_OPS(10) PIK_FLAVOUR_RESTART_OPS(11) PIK_FLAVOUR_RESTART_OPS(12)
-PIK_FLAVOUR_RESTART_OPS(13) PIK_FLAVOUR_RESTART_OPS(14) PIK_FLAVOUR_RESTART_OPS(15) PIK_FLAVOUR_RESTART_OPS(16)
-#undef PIK_FLAVOUR_RESTART_OPS
+PIK_DECLARE_OPS_FAMILY(void, launch)
+PIK_DECLARE_OPS_FAMILY(void, path)
+PIK_DECLARE_OPS_FAMILY(void, search)
+PIK_DECLARE_OPS_FAMILY(void, route)
+PIK_DECLARE_OPS_FAMILY(void, restart)
 } // namespace pik_exact
-// ... and the kernels specialised for the common configuration (flavour -DPIK_COMMON=1, namespace pik_common;
-// pik_math.hpp says what that is and what it buys)
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
-#define PIK_COMMON_OPS(N) const void* launch_ops_d##N();
-PIK_COMMON_OPS(1) PIK_COMMON_OPS(2) PIK_COMMON_OPS(3) PIK_COMMON_OPS(4) PIK_COMMON_OPS(5) PIK_COMMON_OPS(6)
-PIK_COMMON_OPS(7) PIK_COMMON_OPS(8) PIK_COMMON_OPS(9) PIK_COMMON_OPS(10) PIK_COMMON_OPS(11) PIK_COMMON_OPS(12)
-PIK_COMMON_OPS(13) PIK_COMMON_OPS(14) PIK_COMMON_OPS(15) PIK_COMMON_OPS(16)
-#undef PIK_COMMON_OPS
-#define PIK_FLAVOUR_ROUTE_OPS(N) const void* route_ops_d##N();
-PIK_FLAVOUR_ROUTE_OPS(1) PIK_FLAVOUR_ROUTE_OPS(2) PIK_FLAVOUR_ROUTE_OPS(3) PIK_FLAVOUR_ROUTE_OPS(4)
-PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_FLAVOUR_ROUTE_OPS(8)
-PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
-PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
-#undef PIK_FLAVOUR_ROUTE_OPS
-// (... and the restart launcher of global mode, pik_restart_inst.hip: likewise)
-#define PIK_FLAVOUR_RESTART_OPS(N) const void* restart_ops_d##N();
-PIK_FLAVOUR_RESTART_OPS(1) PIK_FLAVOUR_RESTART_OPS(2) PIK_FLAVOUR_RESTART_OPS(3) PIK_FLAVOUR_RESTART_OPS(4)
-PIK_FLAVOUR_RESTART_OPS(5) PIK_FLAVOUR_RESTART_OPS(6) PIK_FLAVOUR_RESTART_OPS(7) PIK_FLAVOUR_RESTART_OPS(8)
-PIK_FLAVOUR_RESTART_OPS(9) PIK_FLAVOUR_RESTART_OPS(10) PIK_FLAVOUR_RESTART_OPS(11) PIK_FLAVOUR_RESTART_OPS(12)
-PIK_FLAVOUR_RESTART_OPS(13) PIK_FLAVOUR_RESTART_OPS(14) PIK_FLAVOUR_RESTART_OPS(15) PIK_FLAVOUR_RESTART_OPS(16)
-#undef PIK_FLAVOUR_RESTART_OPS
+PIK_DECLARE_OPS_FAMILY(void, launch)
+PIK_DECLARE_OPS_FAMILY(void, route)
+PIK_DECLARE_OPS_FAMILY(void, restart)
 } // namespace pik_common
-// ... and the same with the joint goals left in (-DPIK_NO_GOALS=0): BASELINE config 3's kind of call
 namespace pik_common_goals {
 char* error_buffer() { return ::pik::error_buffer(); }
-#define PIK_COMMON_OPS(N) const void* launch_ops_d##N();
-PIK_COMMON_OPS(1) PIK_COMMON_OPS(2) PIK_COMMON_OPS(3) PIK_COMMON_OPS(4) PIK_COMMON_OPS(5) PIK_COMMON_OPS(6)
-PIK_COMMON_OPS(7) PIK_COMMON_OPS(8) PIK_COMMON_OPS(9) PIK_COMMON_OPS(10) PIK_COMMON_OPS(11) PIK_COMMON_OPS(12)
-PIK_COMMON_OPS(13) PIK_COMMON_OPS(14) PIK_COMMON_OPS(15) PIK_COMMON_OPS(16)
-#undef PIK_COMMON_OPS
-#define PIK_FLAVOUR_ROUTE_OPS(N) const void* route_ops_d##N();
-PIK_FLAVOUR_ROUTE_OPS(1) PIK_FLAVOUR_ROUTE_OPS(2) PIK_FLAVOUR_ROUTE_OPS(3) PIK_FLAVOUR_ROUTE_OPS(4)
-PIK_FLAVOUR_ROUTE_OPS(5) PIK_FLAVOUR_ROUTE_OPS(6) PIK_FLAVOUR_ROUTE_OPS(7) PIK_FLAVOUR_ROUTE_OPS(8)
-PIK_FLAVOUR_ROUTE_OPS(9) PIK_FLAVOUR_ROUTE_OPS(10) PIK_FLAVOUR_ROUTE_OPS(11) PIK_FLAVOUR_ROUTE_OPS(12)
-PIK_FLAVOUR_ROUTE_OPS(13) PIK_FLAVOUR_ROUTE_OPS(14) PIK_FLAVOUR_ROUTE_OPS(15) PIK_FLAVOUR_ROUTE_OPS(16)
-#undef PIK_FLAVOUR_ROUTE_OPS
-// (... and the restart launcher of global mode, pik_restart_inst.hip: likewise)
-#define PIK_FLAVOUR_RESTART_OPS(N) const void* restart_ops_d##N();
-PIK_FLAVOUR_RESTART_OPS(1) PIK_FLAVOUR_RESTART_OPS(2) PIK_FLAVOUR_RESTART_OPS(3) PIK_FLAVOUR_RESTART_OPS(4)
-PIK_FLAVOUR_RESTART_OPS(5) PIK_FLAVOUR_RESTART_OPS(6) PIK_FLAVOUR_RESTART_OPS(7) PIK_FLAVOUR_RESTART_OPS(8)
-PIK_FLAVOUR_RESTART_OPS(9) PIK_FLAVOUR_RESTART_OPS(10) PIK_FLAVOUR_RESTART_OPS(11) PIK_FLAVOUR_RESTART_OPS(12)
-PIK_FLAVOUR_RESTART_OPS(13) PIK_FLAVOUR_RESTART_OPS(14) PIK_FLAVOUR_RESTART_OPS(15) PIK_FLAVOUR_RESTART_OPS(16)
-#undef PIK_FLAVOUR_RESTART_OPS
+PIK_DECLARE_OPS_FAMILY(void, launch)
+PIK_DECLARE_OPS_FAMILY(void, route)
+PIK_DECLARE_OPS_FAMILY(void, restart)
 } // namespace pik_common_goals
 #endif
 
 namespace {
+
+// The flavours of kernels this library links, and the families of per-length ops tables each may have.  The product
+// library: the Denavit-Hartenberg kernels (namespace pik), the EXACT kernels (-DPIK_STRICT -DPIK_EXACT_FMA, namespace
+// pik_exact: MoveIt's chain product, the literal 2 dof + 3 cost evaluations per gradient step with the accept
+// evaluation's work re-used, IEEE square roots and divisions, fused multiply-adds at stated places -- bit-identical to
+// the oracle's math mode "fma"; they solve the chains the Denavit-Hartenberg kernels cannot express and every call of
+// a handle whose option `arithmetic` is `exact`), and the kernels specialised for the common configuration
+// (-DPIK_COMMON=1, namespace pik_common; pik_math.hpp says what that is and what it buys), without and with the joint
+// goals (-DPIK_NO_GOALS=0, namespace pik_common_goals: BASELINE config 3's kind of call).  The verification library:
+// its one flavour (namespace pik_strict, which `pik` names there).
+enum Flavour {
+    FL_HOME, // the namespace this file is compiled in: the general kernels (product) / the strict ones (verification)
+#if !defined(PIK_STRICT)
+    FL_EXACT,
+    FL_COMMON,
+    FL_COMMON_GOALS,
+#endif
+    N_FLAVOURS
+};
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -149,37 +104,42 @@ struct SolverExt : pikamd_solver {
 SolverExt* ext_of(pikamd_solver* s) { return static_cast<SolverExt*>(s); }
 const SolverExt* ext_of(const pikamd_solver* s) { return static_cast<const SolverExt*>(s); }
 
-#if !defined(PIK_STRICT)
-const pik::LaunchOps* literal_ops(int dof) {
-    const void* p = nullptr;
-    switch (dof) {
-#define PIK_LITERAL_CASE(N) case N: p = pik_exact::launch_ops_d##N(); break;
-        PIK_LITERAL_CASE(1) PIK_LITERAL_CASE(2) PIK_LITERAL_CASE(3) PIK_LITERAL_CASE(4) PIK_LITERAL_CASE(5)
-        PIK_LITERAL_CASE(6) PIK_LITERAL_CASE(7) PIK_LITERAL_CASE(8) PIK_LITERAL_CASE(9) PIK_LITERAL_CASE(10)
-        PIK_LITERAL_CASE(11) PIK_LITERAL_CASE(12) PIK_LITERAL_CASE(13) PIK_LITERAL_CASE(14) PIK_LITERAL_CASE(15)
-        PIK_LITERAL_CASE(16)
-#undef PIK_LITERAL_CASE
-        default: break;
-    }
-    return static_cast<const pik::LaunchOps*>(p);
+// Every ops table of the library: [flavour][family] -> the lookup by chain length (<stem>_ops(dof), pik_dofs.hpp), or
+// null where the flavour has no such family.  A lookup gives null for a length outside 1..16 and for one built as a
+// stub (PIK_ONLY_D).
+using OpsLookup = const void* (*)(int dof);
+template <class Ops, const Ops* (*lookup)(int)>
+const void* untyped(int dof) {
+    return lookup(dof);
 }
+const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
+    {untyped<pik::LaunchOps, pik::launch_ops>, untyped<pik::PathOps, pik::path_ops>, untyped<pik::SearchOps, pik::search_ops>,
+#if defined(PIK_STRICT)
+     nullptr, // (no routed launcher)
+#else
+     untyped<pik::RouteOps, pik::route_ops>,
 #endif
+     untyped<pik::RestartOps, pik::restart_ops>},
+#if !defined(PIK_STRICT)
+    {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops},
+#endif
+};
+// ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
+const char* const FLAVOUR_NAMESPACE[N_FLAVOURS] = {
+#if defined(PIK_STRICT)
+    "pik_strict",
+#else
+    "pik", "pik_exact", "pik_common", "pik_common_goals",
+#endif
+};
 
-#if !defined(PIK_STRICT)
-const pik::LaunchOps* common_ops(int dof, bool goals = false) {
-    const void* p = nullptr;
-    switch (dof) {
-#define PIK_COMMON_CASE(N) case N: p = goals ? pik_common_goals::launch_ops_d##N() : pik_common::launch_ops_d##N(); break;
-        PIK_COMMON_CASE(1) PIK_COMMON_CASE(2) PIK_COMMON_CASE(3) PIK_COMMON_CASE(4) PIK_COMMON_CASE(5)
-        PIK_COMMON_CASE(6) PIK_COMMON_CASE(7) PIK_COMMON_CASE(8) PIK_COMMON_CASE(9) PIK_COMMON_CASE(10)
-        PIK_COMMON_CASE(11) PIK_COMMON_CASE(12) PIK_COMMON_CASE(13) PIK_COMMON_CASE(14) PIK_COMMON_CASE(15)
-        PIK_COMMON_CASE(16)
-#undef PIK_COMMON_CASE
-        default: break;
-    }
-    return static_cast<const pik::LaunchOps*>(p);
+template <class Ops>
+const Ops* ops_at(Flavour f, Family family, int dof) {
+    const OpsLookup lookup = OPS_TABLE[f][family];
+    return lookup ? static_cast<const Ops*>(lookup(dof)) : nullptr;
 }
-#endif
 
 int check_solver(const pikamd_solver* s) {
     if (!s) return fail(PIKAMD_EINVAL, "solver handle is NULL");
@@ -203,14 +163,6 @@ int check_solver(const pikamd_solver* s) {
 [[maybe_unused]] bool needs_literal(const pikamd_solver* s, const pikamd_params* p) {
     return needs_literal(s) || (p && p->gd_step_size > 1.0e-2);
 }
-const pik::LaunchOps* ops_of(const pikamd_solver* s, const pikamd_params* p = nullptr) {
-#if !defined(PIK_STRICT)
-    if (needs_literal(s, p)) return literal_ops(s->chain.dof);
-#else
-    (void)p;
-#endif
-    return pik::launch_ops(s->chain.dof);
-}
 
 // Does this call have the common configuration (pik_math.hpp PIK_COMMON)?  Chain: every variable a bounded
 // revolute joint, no general Denavit-Hartenberg step -- on every tip's path; parameters: both pose-cost terms
@@ -225,20 +177,51 @@ const pik::LaunchOps* ops_of(const pikamd_solver* s, const pikamd_params* p = nu
     if (!chain_ok(s->chain)) return false;
     for (int k = 1; k < s->n_tips; ++k)
         if (!chain_ok(s->more[k - 1])) return false;
-    // (a joint goal enabled: the flavour with the goals left in, see solve_ops_of)
     if (pk.line_delta == 0 || !(pk.pos_scale > 0.0) || !(pk.rot_scale > 0.0)) return false;
     if (p->mode == 0 && (pk.elites != 4 || p->memetic_num_threads > 1)) return false;
     return true;
 }
-// the kernels of one solve call
-const pik::LaunchOps* solve_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
-#if !defined(PIK_STRICT)
-    if (common_eligible(s, p, pk))
-        if (const pik::LaunchOps* o = common_ops(s->chain.dof, pk.goal_mask != 0)) return o;
+
+// THE flavour of a call: everything that picks kernels or reports their name asks here.  pk: the call's converted
+// parameters -- or null, for a call the common flavours never serve (the parity hooks, paths, searches) or whose
+// parameters do not convert.
+//
+// The common flavours are asked for first, the literal kernels second.  The order does not matter: a call cannot
+// qualify for both.  common_eligible requires pk.line_delta != 0, which make_params_k (pik_host.hpp) sets only for
+// gd_step_size <= 1e-3; needs_literal(s, p) beyond needs_literal(s) -- which common_eligible excludes itself -- asks
+// for gd_step_size > 1e-2.  So common_eligible implies !needs_literal(s, p) as long as the first threshold is not
+// above the second (tests/test_build_cpu.py reads both from the sources and holds them to that).
+Flavour flavour_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK* pk) {
+#if defined(PIK_STRICT)
+    (void)s, (void)p, (void)pk;
+    return FL_HOME;
 #else
-    (void)pk;
+    if (pk && common_eligible(s, p, *pk)) return pk->goal_mask != 0 ? FL_COMMON_GOALS : FL_COMMON;
+    return needs_literal(s, p) ? FL_EXACT : FL_HOME;
 #endif
-    return ops_of(s, p);
+}
+// is it one of the common-configuration flavours; the flavour that serves the call where those have no kernels (a
+// length built as a stub -- a path or a search never asks for them); does it run the exact flavours' kernel variants
+bool is_common(Flavour f) {
+#if defined(PIK_STRICT)
+    (void)f;
+    return false;
+#else
+    return f == FL_COMMON || f == FL_COMMON_GOALS;
+#endif
+}
+Flavour unspecialised(Flavour f) { return is_common(f) ? FL_HOME : f; }
+bool is_exact(Flavour f) { return pik::EXACT_FLAVOUR || (f != FL_HOME && !is_common(f)); }
+
+// the kernels of the parity hooks (no ParamsK: never the common flavours) ...
+const pik::LaunchOps* ops_of(const pikamd_solver* s, const pikamd_params* p = nullptr) {
+    return ops_at<pik::LaunchOps>(flavour_of(s, p, nullptr), FAM_LAUNCH, s->chain.dof);
+}
+// ... and of one solve call
+const pik::LaunchOps* solve_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
+    const Flavour f = flavour_of(s, p, &pk);
+    if (const pik::LaunchOps* o = ops_at<pik::LaunchOps>(f, FAM_LAUNCH, s->chain.dof)) return o;
+    return ops_at<pik::LaunchOps>(unspecialised(f), FAM_LAUNCH, s->chain.dof);
 }
 
 // The routed launcher of one solve call (pik_route.hpp: the regime of every pass chosen on the device), in the
@@ -246,31 +229,12 @@ const pik::LaunchOps* solve_ops_of(const pikamd_solver* s, const pikamd_params* 
 // one species, nothing forced (lanes per elite, their schedule, the regime) and the option device_regime on; whether
 // the call has a compaction pass to route the launcher finds out itself (RouteCtx::served).  The verification library
 // has no routed launcher.
-[[maybe_unused]] const pik::RouteOps* route_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
-#if !defined(PIK_STRICT)
+const pik::RouteOps* route_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
     const pik::SolverOptions& o = s->opt;
     if (!ext_of(s)->device_regime || p->mode != 0 || s->n_tips != 1 || p->memetic_num_threads > 1 || o.lpe != 0 ||
         o.n_sched != 0 || o.regime != 0)
         return nullptr;
-    const bool common = common_eligible(s, p, pk), goals = pk.goal_mask != 0, literal = needs_literal(s, p);
-    const void* r = nullptr;
-    switch (s->chain.dof) {
-#define PIK_ROUTE_CASE(N)                                                                                             \
-    case N:                                                                                                           \
-        r = common ? (goals ? pik_common_goals::route_ops_d##N() : pik_common::route_ops_d##N())                      \
-                   : literal ? pik_exact::route_ops_d##N() : static_cast<const void*>(pik::route_ops_d##N());         \
-        break;
-        PIK_ROUTE_CASE(1) PIK_ROUTE_CASE(2) PIK_ROUTE_CASE(3) PIK_ROUTE_CASE(4) PIK_ROUTE_CASE(5) PIK_ROUTE_CASE(6)
-        PIK_ROUTE_CASE(7) PIK_ROUTE_CASE(8) PIK_ROUTE_CASE(9) PIK_ROUTE_CASE(10) PIK_ROUTE_CASE(11) PIK_ROUTE_CASE(12)
-        PIK_ROUTE_CASE(13) PIK_ROUTE_CASE(14) PIK_ROUTE_CASE(15) PIK_ROUTE_CASE(16)
-#undef PIK_ROUTE_CASE
-        default: break;
-    }
-    return static_cast<const pik::RouteOps*>(r);
-#else
-    (void)s, (void)p, (void)pk;
-    return nullptr;
-#endif
+    return ops_at<pik::RouteOps>(flavour_of(s, p, &pk), FAM_ROUTE, s->chain.dof);
 }
 
 // one solve call: the routed launcher where the call is of its kind, launch_solve otherwise
@@ -294,73 +258,17 @@ int no_kernels(int dof) {
     return fail(PIKAMD_EUNSUPPORTED, "dof %d: kernels are instantiated for 1..16", dof);
 }
 
-// the waypoint-path kernels of a call: the flavour ops_of picks (a call with the common configuration: the general one)
+// the waypoint-path kernels of a call, the restart-search kernels of a call: the flavour ops_of picks (a call with the
+// common configuration: the general one) ...
 const pik::PathOps* path_ops_of(const pikamd_solver* s, const pikamd_params* p) {
-#if !defined(PIK_STRICT)
-    if (needs_literal(s, p)) {
-        const void* o = nullptr;
-        switch (s->chain.dof) {
-#define PIK_LITERAL_PATH_CASE(N) case N: o = pik_exact::path_ops_d##N(); break;
-            PIK_LITERAL_PATH_CASE(1) PIK_LITERAL_PATH_CASE(2) PIK_LITERAL_PATH_CASE(3) PIK_LITERAL_PATH_CASE(4)
-            PIK_LITERAL_PATH_CASE(5) PIK_LITERAL_PATH_CASE(6) PIK_LITERAL_PATH_CASE(7) PIK_LITERAL_PATH_CASE(8)
-            PIK_LITERAL_PATH_CASE(9) PIK_LITERAL_PATH_CASE(10) PIK_LITERAL_PATH_CASE(11) PIK_LITERAL_PATH_CASE(12)
-            PIK_LITERAL_PATH_CASE(13) PIK_LITERAL_PATH_CASE(14) PIK_LITERAL_PATH_CASE(15) PIK_LITERAL_PATH_CASE(16)
-#undef PIK_LITERAL_PATH_CASE
-            default: break;
-        }
-        return static_cast<const pik::PathOps*>(o);
-    }
-#else
-    (void)p;
-#endif
-    return pik::path_ops(s->chain.dof);
+    return ops_at<pik::PathOps>(flavour_of(s, p, nullptr), FAM_PATH, s->chain.dof);
 }
-
-// ... and the restart-search kernels of a call, by the same rule
 const pik::SearchOps* search_ops_of(const pikamd_solver* s, const pikamd_params* p) {
-#if !defined(PIK_STRICT)
-    if (needs_literal(s, p)) {
-        const void* o = nullptr;
-        switch (s->chain.dof) {
-#define PIK_LITERAL_SEARCH_CASE(N) case N: o = pik_exact::search_ops_d##N(); break;
-            PIK_LITERAL_SEARCH_CASE(1) PIK_LITERAL_SEARCH_CASE(2) PIK_LITERAL_SEARCH_CASE(3) PIK_LITERAL_SEARCH_CASE(4)
-            PIK_LITERAL_SEARCH_CASE(5) PIK_LITERAL_SEARCH_CASE(6) PIK_LITERAL_SEARCH_CASE(7) PIK_LITERAL_SEARCH_CASE(8)
-            PIK_LITERAL_SEARCH_CASE(9) PIK_LITERAL_SEARCH_CASE(10) PIK_LITERAL_SEARCH_CASE(11) PIK_LITERAL_SEARCH_CASE(12)
-            PIK_LITERAL_SEARCH_CASE(13) PIK_LITERAL_SEARCH_CASE(14) PIK_LITERAL_SEARCH_CASE(15) PIK_LITERAL_SEARCH_CASE(16)
-#undef PIK_LITERAL_SEARCH_CASE
-            default: break;
-        }
-        return static_cast<const pik::SearchOps*>(o);
-    }
-#else
-    (void)p;
-#endif
-    return pik::search_ops(s->chain.dof);
+    return ops_at<pik::SearchOps>(flavour_of(s, p, nullptr), FAM_SEARCH, s->chain.dof);
 }
-
 // ... and the restart launcher of a global-mode call (pik_restart.hpp), in the flavour solve_ops_of picks
 const pik::RestartOps* restart_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
-#if !defined(PIK_STRICT)
-    const bool common = common_eligible(s, p, pk), goals = pk.goal_mask != 0, literal = needs_literal(s, p);
-    const void* r = nullptr;
-    switch (s->chain.dof) {
-#define PIK_RESTART_CASE(N)                                                                                           \
-    case N:                                                                                                           \
-        r = common ? (goals ? pik_common_goals::restart_ops_d##N() : pik_common::restart_ops_d##N())                  \
-                   : literal ? pik_exact::restart_ops_d##N() : static_cast<const void*>(pik::restart_ops_d##N());     \
-        break;
-        PIK_RESTART_CASE(1) PIK_RESTART_CASE(2) PIK_RESTART_CASE(3) PIK_RESTART_CASE(4) PIK_RESTART_CASE(5)
-        PIK_RESTART_CASE(6) PIK_RESTART_CASE(7) PIK_RESTART_CASE(8) PIK_RESTART_CASE(9) PIK_RESTART_CASE(10)
-        PIK_RESTART_CASE(11) PIK_RESTART_CASE(12) PIK_RESTART_CASE(13) PIK_RESTART_CASE(14) PIK_RESTART_CASE(15)
-        PIK_RESTART_CASE(16)
-#undef PIK_RESTART_CASE
-        default: break;
-    }
-    return static_cast<const pik::RestartOps*>(r);
-#else
-    (void)p, (void)pk;
-    return pik::restart_ops(s->chain.dof);
-#endif
+    return ops_at<pik::RestartOps>(flavour_of(s, p, &pk), FAM_RESTART, s->chain.dof);
 }
 
 size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
@@ -406,7 +314,7 @@ static int32_t create_solver(const pik::ChainHost* chains, int n_tips, int32_t d
         return fail(PIKAMD_ENODEVICE, "no HIP device available (this library has no CPU path)");
     if (device_ordinal < 0 || device_ordinal >= count)
         return fail(PIKAMD_EINVAL, "device_ordinal %d out of range [0, %d)", device_ordinal, count);
-    if (!pik::launch_ops(chains[0].dof)) return no_kernels(chains[0].dof);
+    if (!ops_at<pik::LaunchOps>(FL_HOME, FAM_LAUNCH, chains[0].dof)) return no_kernels(chains[0].dof);
     HIP_TRY(hipSetDevice(device_ordinal));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device_ordinal));
@@ -1245,7 +1153,7 @@ int32_t pikamd_self_test(pikamd_solver* s, const pikamd_params* p, int32_t n, ui
     if (n < 1 || n > 4096) return fail(PIKAMD_EINVAL, "n out of range [1, 4096]");
     // the flavour under test: the exact kernels (this library is the verification build, the option "arithmetic" =
     // exact, or a chain only they serve) or the product flavours' -- each keeps its own mask of switched-off widths
-    const bool exact_now = pik::EXACT_FLAVOUR || s->opt.exact || needs_literal(s, p);
+    const bool exact_now = is_exact(flavour_of(s, p, nullptr));
     auto mask_of = [exact_now](pik::SolverOptions& o) -> unsigned& { return exact_now ? o.disabled_lanes_exact : o.disabled_lanes; };
     if (disabled_out) *disabled_out = mask_of(s->opt);
     const int d = s->chain.dof, tips = s->n_tips;
@@ -1342,11 +1250,10 @@ int32_t pikamd_self_test(pikamd_solver* s, const pikamd_params* p, int32_t n, ui
             if (!same(ref, got)) disabled |= (unsigned)lanes;
         }
     }
-#if !defined(PIK_STRICT)
     // the kernels specialised for the common configuration against the general ones (when this call has it)
     {
         pik::ParamsK pk;
-        if (!pik::make_params_k(p, pk) && common_eligible(s, p, pk)) {
+        if (!pik::make_params_k(p, pk) && is_common(flavour_of(s, p, &pk))) {
             const bool was = s->opt.specialised;
             s->opt.specialised = false;
             Out general;
@@ -1358,7 +1265,6 @@ int32_t pikamd_self_test(pikamd_solver* s, const pikamd_params* p, int32_t n, ui
             if (!same(ref, general)) disabled |= 32u;
         }
     }
-#endif
     // the two-per-SIMD build of the one-lane kernel, forced whatever the size of the call (one species, one tip)
     if (S == 1 && !multi) {
         if (int rc = run(1, false, true, got)) return rc;
@@ -1392,9 +1298,10 @@ static int maybe_self_test(pikamd_solver* s, const pikamd_params* p) {
     if (!s->opt.auto_self_test || s->in_self_test || !p) return 0;
     pik::ParamsK pk;
     if (pik::make_params_k(p, pk)) return 0; // (the solve itself reports the bad parameter)
-#if !defined(PIK_STRICT)
-    if (common_eligible(s, p, pk) && common_ops(s->chain.dof, pk.goal_mask != 0)) return 0;
-#endif
+    {
+        const Flavour f = flavour_of(s, p, &pk);
+        if (is_common(f) && ops_at<pik::LaunchOps>(f, FAM_LAUNCH, s->chain.dof)) return 0;
+    }
     // One run per KERNEL SET, not per parameter set: what selects the kernels and the paths inside them is the
     // flavour, the mode, species and elites (how a wavefront is dealt out), which joint goals and cost terms are on,
     // the line-search form and the approximate-solution return -- thresholds, weights, population and budgets do not,
@@ -1437,55 +1344,171 @@ extern "C" {
 const char* pikamd_kernel_name(const pikamd_solver* s, const pikamd_params* p) {
     if (!s || !p) return "";
     pikamd_solver* m = const_cast<pikamd_solver*>(s);
-    // the flavour that serves a solve call with these parameters (see solve_ops_of)
-    const char* ns = "pik";
-#if defined(PIK_STRICT)
-    ns = "pik_strict";
-#else
+    // the flavour that serves a solve call with these parameters (see solve_ops_of: a common flavour only where it
+    // has kernels for the length)
     pik::ParamsK pk;
-    if (needs_literal(s, p)) ns = "pik_exact";
-    else if (!pik::make_params_k(p, pk) && common_eligible(s, p, pk) && common_ops(s->chain.dof, pk.goal_mask != 0))
-        ns = pk.goal_mask != 0 ? "pik_common_goals" : "pik_common";
-#endif
-    snprintf(m->kernel_name, sizeof m->kernel_name, "%s::%s<%d>", ns,
+    Flavour f = flavour_of(s, p, pik::make_params_k(p, pk) ? nullptr : &pk);
+    if (!ops_at<pik::LaunchOps>(f, FAM_LAUNCH, s->chain.dof)) f = unspecialised(f);
+    snprintf(m->kernel_name, sizeof m->kernel_name, "%s::%s<%d>", FLAVOUR_NAMESPACE[f],
              p->mode == 1 ? "ik_gradient_kernel" : "memetic_kernel", s->chain.dof);
     return m->kernel_name;
 }
 
 } // extern "C"
 
-// ---- Cartesian waypoint paths (pik_path.hpp) ----------------------------------------------------
+// ---- what the path and search entry points share --------------------------------------------------
 namespace {
 
-// what both path entry points refuse; `any_null`: some required array is NULL
-int check_paths(const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, bool any_null, pik::ParamsK& pk) {
+// One of the three kinds of call, for its refusals: its name, the mode it wants and how it says so, the layout of its
+// arrays and the name of its second required one.
+struct CallKind {
+    const char* name;
+    int mode;
+    const char* wants;      // "<name>: <wants>, got mode <m><because>"
+    const char* because;
+    bool paths;             // counts: P paths of W waypoints (else B problems of max_attempts attempts)
+    const char* layout;
+    const char* second;
+};
+const CallKind SOLVE_PATHS = {"pikamd_solve_paths", 1, "waypoint paths are solved in local mode (mode = 1)", "", true,
+                              "[P][W][dof]", "start"};
+const CallKind SEARCH = {"pikamd_search_batch", 1, "restarts are served in local mode (mode = 1)",
+                         ": a restart attempt of the memetic kernels would have to start a first pass from a device-side "
+                         "list of the failed problems, which their launch does not offer",
+                         false, "[B][dof]", "seed"};
+const CallKind SEARCH_GLOBAL = {"pikamd_search_global_batch", 0, "restarts of the memetic solver (mode = 0)",
+                                ": local mode is served by pikamd_search_batch", false, "[B][dof]", "seed"};
+
+// What both entry points of a kind refuse, in this order (it decides which message a doubly-wrong call gets).  n, k: P
+// and W, or B and max_attempts; any_null: some required array is NULL.
+int check_call(const CallKind& c, const pikamd_solver* s, const pikamd_params* p, int64_t n, int32_t k, bool any_null,
+               pik::ParamsK& pk) {
     if (int rc = check_solver(s)) return rc;
     if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
-    if (p->mode != 1)
-        return fail(PIKAMD_EINVAL, "pikamd_solve_paths: waypoint paths are solved in local mode (mode = 1), got mode %d",
-                    (int)p->mode);
-    if (W < 1 || P < 0)
-        return fail(PIKAMD_EINVAL, "pikamd_solve_paths: %lld paths of %d waypoints: expected P >= 0 and W >= 1",
-                    (long long)P, (int)W);
-    if (s->opt.soa)
-        return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_solve_paths (its arrays are [P][W][dof])");
+    if (p->mode != c.mode) return fail(PIKAMD_EINVAL, "%s: %s, got mode %d%s", c.name, c.wants, (int)p->mode, c.because);
+    if (c.paths) {
+        if (k < 1 || n < 0)
+            return fail(PIKAMD_EINVAL, "%s: %lld paths of %d waypoints: expected P >= 0 and W >= 1", c.name, (long long)n, (int)k);
+    } else {
+        if (k < 1 || k > PIKAMD_MAX_ATTEMPTS)
+            return fail(PIKAMD_EINVAL, "%s: max_attempts %d: expected 1..%d", c.name, (int)k, PIKAMD_MAX_ATTEMPTS);
+        if (n < 0) return fail(PIKAMD_EINVAL, "%s: B = %lld: expected B >= 0", c.name, (long long)n);
+    }
+    if (s->opt.soa) return fail(PIKAMD_EINVAL, "joint_layout soa: not with %s (its arrays are %s)", c.name, c.layout);
     if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
-    if (P > 0 && any_null)
-        return fail(PIKAMD_EINVAL, "pikamd_solve_paths: goal_pos_quat, start, solution and status must not be NULL");
+    if (n > 0 && any_null)
+        return fail(PIKAMD_EINVAL, "%s: goal_pos_quat, %s, solution and status must not be NULL", c.name, c.second);
     return 0;
 }
 
-// the flavour that serves a path call of this handle, and whether it is an exact one
-const char* path_flavour(const pikamd_solver* s, const pikamd_params* p, bool* exact) {
-#if defined(PIK_STRICT)
-    (void)s;
-    (void)p;
-    *exact = true;
-    return "pik_strict";
-#else
-    *exact = needs_literal(s, p);
-    return *exact ? "pik_exact" : "pik";
-#endif
+// Staging of a synchronous entry point, through the synchronous entry points' job (as pikamd_solve_batch): the
+// caller's arrays are registered as regions -- the inputs first --, laid out one behind the other (8-byte aligned
+// pieces) in the job's pinned and device buffers, and moved with one copy in before the kernels and one copy out
+// behind them, on the job's stream.
+class Staging {
+  public:
+    static constexpr int SLOT = pik::N_DEVICE_SLOTS + PIKAMD_MAX_HOST_JOBS - 1;
+    Staging(pikamd_solver* s, const char* who) : s_(s), who_(who), J_(s->jobs[PIKAMD_MAX_HOST_JOBS - 1]) {}
+    hipStream_t stream() const { return J_.stream; }
+    // refuses while the job is in flight; the device, and the stream at its first use
+    int begin() {
+        if (J_.pending)
+            return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", PIKAMD_MAX_HOST_JOBS - 1);
+        HIP_TRY(hipSetDevice(s_->device));
+        if (!J_.stream) HIP_TRY(hipStreamCreateWithFlags(&J_.stream, hipStreamNonBlocking));
+        return 0;
+    }
+    // An input (NULL: absent -- no bytes, a null device pointer) or an output (NULL: not copied out, and absent unless
+    // the kernels write it anyway: `always`); returns the region's index for at().
+    int in(const void* src, size_t bytes) { return add({src, nullptr, total_, src ? bytes : 0}, true); }
+    int out(void* dst, size_t bytes, bool always) { return add({nullptr, dst, total_, (dst || always) ? bytes : 0}, false); }
+    // the buffers, once every region is registered
+    int allocate() {
+        if (int rc = J_.dev.ensure(total_)) return rc;
+        return J_.host.ensure(total_);
+    }
+    template <class T>
+    T* at(int region) const {
+        return r_[region].bytes ? reinterpret_cast<T*>((char*)J_.dev.p + r_[region].off) : nullptr;
+    }
+    // the copy in
+    int upload() {
+        for (int i = 0; i < n_; ++i)
+            if (r_[i].src) std::memcpy((char*)J_.host.p + r_[i].off, r_[i].src, r_[i].bytes);
+        HIP_TRY(hipMemcpyAsync(J_.dev.p, J_.host.p, in_bytes_, hipMemcpyHostToDevice, J_.stream));
+        return 0;
+    }
+    // Behind the launch (its return code): the copy out into the caller's arrays.  Work of the call may be in flight
+    // once upload() has run, so the stream is drained before an error of the launch is returned.
+    int finish(int launch_rc) {
+        if (launch_rc) {
+            (void)hipStreamSynchronize(J_.stream);
+            return launch_rc;
+        }
+        char* hb = (char*)J_.host.p;
+        hipError_t e = hipMemcpyAsync(hb + in_bytes_, (char*)J_.dev.p + in_bytes_, total_ - in_bytes_, hipMemcpyDeviceToHost, J_.stream);
+        const hipError_t e2 = hipStreamSynchronize(J_.stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(PIKAMD_EHIP, "%s: %s (its results are lost)", who_, hipGetErrorString(e));
+        for (int i = 0; i < n_; ++i)
+            if (r_[i].dst) std::memcpy(r_[i].dst, hb + r_[i].off, r_[i].bytes);
+        return 0;
+    }
+
+  private:
+    struct Region {
+        const void* src;
+        void* dst;
+        size_t off, bytes;
+    };
+    int add(const Region& r, bool input) {
+        r_[n_] = r;
+        total_ += align8(r.bytes);
+        if (input) in_bytes_ = total_;
+        return n_++;
+    }
+    pikamd_solver* s_;
+    const char* who_;
+    pik::HostJob& J_;
+    Region r_[12];
+    int n_ = 0;
+    size_t in_bytes_ = 0, total_ = 0;
+};
+
+const char* tips_text(const pikamd_solver* s) { return s->n_tips > 1 ? "true" : "false"; }
+
+// the name of the kernel variant a path or search call runs: one lane, a team (exact flavours) or the cooperative descent
+const char* variant_name(const pikamd_solver* s, Flavour f, const char* stem, int lanes) {
+    pikamd_solver* m = const_cast<pikamd_solver*>(s);
+    const char* ns = FLAVOUR_NAMESPACE[f];
+    const int dof = s->chain.dof;
+    if (lanes == 1)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_kernel<%d,%s>", ns, stem, dof, tips_text(s));
+    else if (is_exact(f))
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_team_kernel<%d,%d>", ns, stem, dof, lanes);
+    else
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_wide_kernel<%d,%d,%s>", ns, stem, dof, lanes, tips_text(s));
+    return m->kernel_name;
+}
+
+} // namespace
+
+// ---- Cartesian waypoint paths (pik_path.hpp) ----------------------------------------------------
+namespace {
+
+// the arrays of a path call: host pointers, or device pointers
+struct PathArrays {
+    const double *goal, *start, *max_step;
+    double* solution;
+    int32_t* status;
+    double* cost;
+    pikamd_stats* stats;
+    int32_t* reached;
+    bool required_null() const { return !goal || !start || !solution || !status; }
+};
+
+pik::PathArgs path_args(int64_t P, int32_t W, const PathArrays& d) {
+    return {P, W, 0, d.goal, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
 }
 
 } // namespace
@@ -1496,119 +1519,87 @@ int32_t pikamd_solve_paths_device(pikamd_solver* s, const pikamd_params* p, int6
                                   const double* d_goal_pos_quat, const double* d_start, const double* d_max_joint_step,
                                   double* d_solution, int32_t* d_status, double* d_final_cost, pikamd_stats* d_stats,
                                   int32_t* d_reached, void* stream, int32_t slot) {
+    const PathArrays d = {d_goal_pos_quat, d_start, d_max_joint_step, d_solution, d_status, d_final_cost, d_stats, d_reached};
     pik::ParamsK pk;
-    if (int rc = check_paths(s, p, P, W, !d_goal_pos_quat || !d_start || !d_solution || !d_status, pk)) return rc;
+    if (int rc = check_call(SOLVE_PATHS, s, p, P, W, d.required_null(), pk)) return rc;
     if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
     if (P == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::PathOps* ops = path_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
     HIP_TRY(hipSetDevice(s->device));
-    const pik::PathArgs a = {P, W, 0, d_goal_pos_quat, d_start, d_max_joint_step, d_solution, d_status,
-                             d_final_cost, d_stats, d_reached};
-    return ops->solve(s, pk, a, (hipStream_t)stream, slot);
+    return ops->solve(s, pk, path_args(P, W, d), (hipStream_t)stream, slot);
 }
 
 int32_t pikamd_solve_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, const double* goal_pos_quat,
                            const double* start, const double* max_joint_step, double* solution, int32_t* status,
                            double* final_cost, pikamd_stats* stats, int32_t* reached) {
+    const PathArrays h = {goal_pos_quat, start, max_joint_step, solution, status, final_cost, stats, reached};
     pik::ParamsK pk;
-    if (int rc = check_paths(s, p, P, W, !goal_pos_quat || !start || !solution || !status, pk)) return rc;
+    if (int rc = check_call(SOLVE_PATHS, s, p, P, W, h.required_null(), pk)) return rc;
     if (P == 0) return 0;
     if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
     const pik::PathOps* ops = path_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
-    // staged like pikamd_solve_batch, through the synchronous entry points' job: one copy in, the kernel, one copy out
-    const int job = PIKAMD_MAX_HOST_JOBS - 1;
-    pik::HostJob& J = s->jobs[job];
-    if (J.pending) return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", job);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!J.stream) HIP_TRY(hipStreamCreateWithFlags(&J.stream, hipStreamNonBlocking));
-    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, rows = (size_t)P * (size_t)W;
-    const size_t off_goal = 0, off_start = off_goal + sizeof(double) * g7 * rows;
-    const size_t off_step = off_start + sizeof(double) * d * (size_t)P;
-    const size_t in_bytes = off_step + (max_joint_step ? sizeof(double) * d : 0);
-    const size_t off_solution = in_bytes, off_cost = off_solution + sizeof(double) * d * rows;
-    const size_t off_stats = off_cost + sizeof(double) * rows, off_status = off_stats + sizeof(pikamd_stats) * rows;
-    const size_t off_reached = off_status + align8(sizeof(int32_t) * rows);
-    const size_t total = off_reached + align8(sizeof(int32_t) * (size_t)P);
-    if (int rc = J.dev.ensure(total)) return rc;
-    if (int rc = J.host.ensure(total)) return rc;
-    char* hb = (char*)J.host.p;
-    char* db = (char*)J.dev.p;
-    std::memcpy(hb + off_goal, goal_pos_quat, sizeof(double) * g7 * rows);
-    std::memcpy(hb + off_start, start, sizeof(double) * d * (size_t)P);
-    if (max_joint_step) std::memcpy(hb + off_step, max_joint_step, sizeof(double) * d);
-    HIP_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, J.stream));
-    const pik::PathArgs a = {P, W, 0, (const double*)(db + off_goal), (const double*)(db + off_start),
-                             max_joint_step ? (const double*)(db + off_step) : nullptr, (double*)(db + off_solution),
-                             (int*)(db + off_status), (double*)(db + off_cost), (void*)(db + off_stats),
-                             (int*)(db + off_reached)};
-    // (work of this call may be in flight from here on: the stream is drained before an error is returned)
-    if (int rc = ops->solve(s, pk, a, J.stream, pik::N_DEVICE_SLOTS + job)) {
-        (void)hipStreamSynchronize(J.stream);
-        return rc;
-    }
-    {
-        hipError_t e = hipMemcpyAsync(hb + in_bytes, db + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, J.stream);
-        const hipError_t e2 = hipStreamSynchronize(J.stream);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) return fail(PIKAMD_EHIP, "pikamd_solve_paths: %s (its results are lost)", hipGetErrorString(e));
-    }
-    std::memcpy(solution, hb + off_solution, sizeof(double) * d * rows);
-    std::memcpy(status, hb + off_status, sizeof(int32_t) * rows);
-    if (final_cost) std::memcpy(final_cost, hb + off_cost, sizeof(double) * rows);
-    if (stats) std::memcpy(stats, hb + off_stats, sizeof(pikamd_stats) * rows);
-    if (reached) std::memcpy(reached, hb + off_reached, sizeof(int32_t) * (size_t)P);
-    return 0;
+    Staging st(s, SOLVE_PATHS.name);
+    if (int rc = st.begin()) return rc;
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
+    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), start_ = st.in(h.start, sizeof(double) * d * paths);
+    const int step = st.in(h.max_step, sizeof(double) * d);
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, true);
+    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, true), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, true);
+    if (int rc = st.allocate()) return rc;
+    const PathArrays dev = {st.at<const double>(goal), st.at<const double>(start_), st.at<const double>(step),
+                            st.at<double>(sol),        st.at<int32_t>(status_),     st.at<double>(cost),
+                            st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_)};
+    if (int rc = st.upload()) return rc;
+    return st.finish(ops->solve(s, pk, path_args(P, W, dev), st.stream(), Staging::SLOT));
 }
 
 const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
     if (!s || !p) return "";
-    pikamd_solver* m = const_cast<pikamd_solver*>(s);
-    bool exact = false;
-    const char* ns = path_flavour(s, p, &exact);
-    const int lanes = pik::path_lanes(s, P, exact), dof = s->chain.dof;
-    if (lanes == 1)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_kernel<%d,%s>", ns, dof, s->n_tips > 1 ? "true" : "false");
-    else if (exact)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_team_kernel<%d,%d>", ns, dof, lanes);
-    else
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_path_wide_kernel<%d,%d,%s>", ns, dof, lanes,
-                 s->n_tips > 1 ? "true" : "false");
-    return m->kernel_name;
+    const Flavour f = flavour_of(s, p, nullptr);
+    return variant_name(s, f, "path", pik::path_lanes(s, P, is_exact(f)));
 }
 
 } // extern "C"
 
-// ---- local IK with random restarts (pik_search.hpp) ----------------------------------------------
+// ---- local IK with random restarts (pik_search.hpp), memetic IK with random restarts (pik_restart.hpp) ----
 namespace {
 
-// what both search entry points refuse; `any_null`: some required array is NULL
-int check_search(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t K, bool any_null, pik::ParamsK& pk) {
-    if (int rc = check_solver(s)) return rc;
-    if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
-    if (p->mode != 1)
-        return fail(PIKAMD_EINVAL,
-                    "pikamd_search_batch: restarts are served in local mode (mode = 1), got mode %d: a restart attempt of "
-                    "the memetic kernels would have to start a first pass from a device-side list of the failed problems, "
-                    "which their launch does not offer",
-                    (int)p->mode);
-    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
-        return fail(PIKAMD_EINVAL, "pikamd_search_batch: max_attempts %d: expected 1..%d", (int)K, PIKAMD_MAX_ATTEMPTS);
-    if (B < 0) return fail(PIKAMD_EINVAL, "pikamd_search_batch: B = %lld: expected B >= 0", (long long)B);
-    if (s->opt.soa)
-        return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_search_batch (its arrays are [B][dof])");
-    if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
-    if (B > 0 && any_null)
-        return fail(PIKAMD_EINVAL, "pikamd_search_batch: goal_pos_quat, seed, solution and status must not be NULL");
+// the arrays of a search call of either mode: host pointers, or device pointers
+struct SearchArrays {
+    const double *goal, *seed, *guess; // guess: null = the seed
+    double* solution;
+    int32_t* status;
+    double* cost;
+    pikamd_stats* stats;
+    int32_t* attempts;
+    double* all_solution;
+    int32_t* all_status;
+    bool required_null() const { return !goal || !seed || !solution || !status; }
+};
+
+// registers the arrays of a synchronous search call of B problems and K attempts, allocates, and gives the device's
+int stage_search(Staging& st, const pikamd_solver* s, const SearchArrays& h, int64_t B, int32_t K, SearchArrays& dev) {
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, n = (size_t)B, rows = n * (size_t)K;
+    const int goal = st.in(h.goal, sizeof(double) * g7 * n), seed = st.in(h.seed, sizeof(double) * d * n);
+    const int guess = st.in(h.guess, sizeof(double) * d * n);
+    const int sol = st.out(h.solution, sizeof(double) * d * n, true), cost = st.out(h.cost, sizeof(double) * n, true);
+    const int stats = st.out(h.stats, sizeof(pikamd_stats) * n, true), status = st.out(h.status, sizeof(int32_t) * n, true);
+    const int attempts = st.out(h.attempts, sizeof(int32_t) * n, true);
+    const int all_sol = st.out(h.all_solution, sizeof(double) * d * rows, false);
+    const int all_status = st.out(h.all_status, sizeof(int32_t) * rows, false);
+    if (int rc = st.allocate()) return rc;
+    dev = {st.at<const double>(goal), st.at<const double>(seed), st.at<const double>(guess), st.at<double>(sol),
+           st.at<int32_t>(status),    st.at<double>(cost),       st.at<pikamd_stats>(stats), st.at<int32_t>(attempts),
+           st.at<double>(all_sol),    st.at<int32_t>(all_status)};
     return 0;
 }
 
 pik::SearchPlan search_plan_of(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t K) {
-    bool exact = false;
-    (void)path_flavour(s, p, &exact);
-    return pik::search_plan(s, ext_of(s)->search_schedule, B, K, exact);
+    return pik::search_plan(s, ext_of(s)->search_schedule, B, K, is_exact(flavour_of(s, p, nullptr)));
 }
 
 // Schedule, width and -- parallel schedule -- the per-attempt rows of a call: the caller's all_* arrays where given,
@@ -1639,6 +1630,43 @@ int plan_search(pikamd_solver* s, const pikamd_params* p, int slot, pik::SearchA
     return 0;
 }
 
+// the arguments of a local-mode search on device pointers, planned (plan_search: may grow the slot's scratch)
+int search_args(pikamd_solver* s, const pikamd_params* p, int slot, int64_t B, int32_t K, const SearchArrays& d,
+                uint64_t rng_seed, int64_t problem_offset, pik::SearchArgs& a) {
+    a = {};
+    a.B = B;
+    a.K = K;
+    a.goal = d.goal;
+    a.seed = d.seed;
+    a.guess = d.guess ? d.guess : d.seed;
+    a.rng_seed = rng_seed;
+    a.problem_offset = problem_offset;
+    a.solution = d.solution;
+    a.status = d.status;
+    a.cost = d.cost;
+    a.stats = d.stats;
+    a.attempts = d.attempts;
+    return plan_search(s, p, slot, a, d.all_solution, d.all_status);
+}
+
+// ... and of a global-mode one (goal and seed apart: they go to the solver)
+pik::RestartArgs restart_args(int64_t B, int32_t K, const SearchArrays& d, uint64_t rng_seed, int64_t problem_offset) {
+    pik::RestartArgs r = {};
+    r.B = B;
+    r.K = K;
+    r.user_guess = d.guess ? d.guess : d.seed;
+    r.rng_seed = rng_seed;
+    r.problem_offset = problem_offset;
+    r.solution = d.solution;
+    r.status = d.status;
+    r.cost = d.cost;
+    r.stats = d.stats;
+    r.attempts = d.attempts;
+    r.all_solution = d.all_solution;
+    r.all_status = d.all_status;
+    return r;
+}
+
 } // namespace
 
 extern "C" {
@@ -1648,28 +1676,18 @@ int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int
                                    int64_t problem_offset, int32_t max_attempts, double* d_solution, int32_t* d_status,
                                    double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
                                    double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot) {
+    const SearchArrays d = {d_goal_pos_quat, d_seed,  d_initial_guess, d_solution,     d_status,
+                            d_final_cost,    d_stats, d_attempts,      d_all_solution, d_all_status};
     pik::ParamsK pk;
-    if (int rc = check_search(s, p, B, max_attempts, !d_goal_pos_quat || !d_seed || !d_solution || !d_status, pk)) return rc;
+    if (int rc = check_call(SEARCH, s, p, B, max_attempts, d.required_null(), pk)) return rc;
     if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
     if (B == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::SearchOps* ops = search_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
     HIP_TRY(hipSetDevice(s->device));
-    pik::SearchArgs a = {};
-    a.B = B;
-    a.K = max_attempts;
-    a.goal = d_goal_pos_quat;
-    a.seed = d_seed;
-    a.guess = d_initial_guess ? d_initial_guess : d_seed;
-    a.rng_seed = rng_seed;
-    a.problem_offset = problem_offset;
-    a.solution = d_solution;
-    a.status = d_status;
-    a.cost = d_final_cost;
-    a.stats = d_stats;
-    a.attempts = d_attempts;
-    if (int rc = plan_search(s, p, slot, a, d_all_solution, d_all_status)) return rc;
+    pik::SearchArgs a;
+    if (int rc = search_args(s, p, slot, B, max_attempts, d, rng_seed, problem_offset, a)) return rc;
     return ops->solve(s, pk, a, (hipStream_t)stream, slot);
 }
 
@@ -1677,117 +1695,35 @@ int32_t pikamd_search_batch(pikamd_solver* s, const pikamd_params* p, int64_t B,
                             const double* seed, const double* initial_guess, uint64_t rng_seed, int64_t problem_offset,
                             int32_t max_attempts, double* solution, int32_t* status, double* final_cost,
                             pikamd_stats* stats, int32_t* attempts, double* all_solution, int32_t* all_status) {
+    const SearchArrays h = {goal_pos_quat, seed, initial_guess, solution, status, final_cost, stats, attempts, all_solution, all_status};
     pik::ParamsK pk;
-    if (int rc = check_search(s, p, B, max_attempts, !goal_pos_quat || !seed || !solution || !status, pk)) return rc;
+    if (int rc = check_call(SEARCH, s, p, B, max_attempts, h.required_null(), pk)) return rc;
     if (B == 0) return 0;
     if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
     const pik::SearchOps* ops = search_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
-    // staged like pikamd_solve_paths, through the synchronous entry points' job: one copy in, the kernels, one copy out
-    const int job = PIKAMD_MAX_HOST_JOBS - 1;
-    pik::HostJob& J = s->jobs[job];
-    if (J.pending) return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", job);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!J.stream) HIP_TRY(hipStreamCreateWithFlags(&J.stream, hipStreamNonBlocking));
-    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, n = (size_t)B, rows = n * (size_t)max_attempts;
-    const size_t off_goal = 0, off_seed = off_goal + sizeof(double) * g7 * n, off_guess = off_seed + sizeof(double) * d * n;
-    const size_t in_bytes = off_guess + (initial_guess ? sizeof(double) * d * n : 0);
-    const size_t off_solution = in_bytes, off_cost = off_solution + sizeof(double) * d * n;
-    const size_t off_stats = off_cost + sizeof(double) * n, off_status = off_stats + sizeof(pikamd_stats) * n;
-    const size_t off_attempts = off_status + align8(sizeof(int32_t) * n);
-    const size_t off_all_solution = off_attempts + align8(sizeof(int32_t) * n);
-    const size_t off_all_status = off_all_solution + (all_solution ? sizeof(double) * d * rows : 0);
-    const size_t total = off_all_status + (all_status ? align8(sizeof(int32_t) * rows) : 0);
-    if (int rc = J.dev.ensure(total)) return rc;
-    if (int rc = J.host.ensure(total)) return rc;
-    char* hb = (char*)J.host.p;
-    char* db = (char*)J.dev.p;
-    pik::SearchArgs a = {};
-    a.B = B;
-    a.K = max_attempts;
-    a.goal = (const double*)(db + off_goal);
-    a.seed = (const double*)(db + off_seed);
-    a.guess = initial_guess ? (const double*)(db + off_guess) : a.seed;
-    a.rng_seed = rng_seed;
-    a.problem_offset = problem_offset;
-    a.solution = (double*)(db + off_solution);
-    a.status = (int*)(db + off_status);
-    a.cost = (double*)(db + off_cost);
-    a.stats = (void*)(db + off_stats);
-    a.attempts = (int*)(db + off_attempts);
-    const int slot = pik::N_DEVICE_SLOTS + job;
-    if (int rc = plan_search(s, p, slot, a, all_solution ? (double*)(db + off_all_solution) : nullptr,
-                             all_status ? (int32_t*)(db + off_all_status) : nullptr))
-        return rc;
-    std::memcpy(hb + off_goal, goal_pos_quat, sizeof(double) * g7 * n);
-    std::memcpy(hb + off_seed, seed, sizeof(double) * d * n);
-    if (initial_guess) std::memcpy(hb + off_guess, initial_guess, sizeof(double) * d * n);
-    HIP_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, J.stream));
-    // (work of this call may be in flight from here on: the stream is drained before an error is returned)
-    if (int rc = ops->solve(s, pk, a, J.stream, slot)) {
-        (void)hipStreamSynchronize(J.stream);
-        return rc;
-    }
-    {
-        hipError_t e = hipMemcpyAsync(hb + in_bytes, db + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, J.stream);
-        const hipError_t e2 = hipStreamSynchronize(J.stream);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) return fail(PIKAMD_EHIP, "pikamd_search_batch: %s (its results are lost)", hipGetErrorString(e));
-    }
-    std::memcpy(solution, hb + off_solution, sizeof(double) * d * n);
-    std::memcpy(status, hb + off_status, sizeof(int32_t) * n);
-    if (final_cost) std::memcpy(final_cost, hb + off_cost, sizeof(double) * n);
-    if (stats) std::memcpy(stats, hb + off_stats, sizeof(pikamd_stats) * n);
-    if (attempts) std::memcpy(attempts, hb + off_attempts, sizeof(int32_t) * n);
-    if (all_solution) std::memcpy(all_solution, hb + off_all_solution, sizeof(double) * d * rows);
-    if (all_status) std::memcpy(all_status, hb + off_all_status, sizeof(int32_t) * rows);
-    return 0;
+    Staging st(s, SEARCH.name);
+    if (int rc = st.begin()) return rc;
+    SearchArrays d;
+    if (int rc = stage_search(st, s, h, B, max_attempts, d)) return rc;
+    pik::SearchArgs a;
+    if (int rc = search_args(s, p, Staging::SLOT, B, max_attempts, d, rng_seed, problem_offset, a)) return rc;
+    if (int rc = st.upload()) return rc;
+    return st.finish(ops->solve(s, pk, a, st.stream(), Staging::SLOT));
 }
 
 const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t max_attempts,
                                       int32_t* attempts_in_flight) {
     if (attempts_in_flight) *attempts_in_flight = 0;
     if (!s || !p || B < 0 || max_attempts < 1 || max_attempts > PIKAMD_MAX_ATTEMPTS) return "";
-    pikamd_solver* m = const_cast<pikamd_solver*>(s);
-    bool exact = false;
-    const char* ns = path_flavour(s, p, &exact);
     const pik::SearchPlan plan = search_plan_of(s, p, B, max_attempts);
-    const int lanes = plan.lanes, dof = s->chain.dof;
     if (attempts_in_flight) *attempts_in_flight = plan.parallel ? max_attempts : 1;
-    if (lanes == 1)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_kernel<%d,%s>", ns, dof, s->n_tips > 1 ? "true" : "false");
-    else if (exact)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_team_kernel<%d,%d>", ns, dof, lanes);
-    else
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_search_wide_kernel<%d,%d,%s>", ns, dof, lanes,
-                 s->n_tips > 1 ? "true" : "false");
-    return m->kernel_name;
+    return variant_name(s, flavour_of(s, p, nullptr), "search", plan.lanes);
 }
 
 } // extern "C"
 
-// ---- memetic IK with random restarts (pik_restart.hpp) --------------------------------------------
 namespace {
-
-int check_search_global(const pikamd_solver* s, const pikamd_params* p, int64_t B, int32_t K, bool any_null,
-                        pik::ParamsK& pk) {
-    if (int rc = check_solver(s)) return rc;
-    if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
-    if (p->mode != 0)
-        return fail(PIKAMD_EINVAL,
-                    "pikamd_search_global_batch: restarts of the memetic solver (mode = 0), got mode %d: local mode is "
-                    "served by pikamd_search_batch",
-                    (int)p->mode);
-    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
-        return fail(PIKAMD_EINVAL, "pikamd_search_global_batch: max_attempts %d: expected 1..%d", (int)K, PIKAMD_MAX_ATTEMPTS);
-    if (B < 0) return fail(PIKAMD_EINVAL, "pikamd_search_global_batch: B = %lld: expected B >= 0", (long long)B);
-    if (s->opt.soa)
-        return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_search_global_batch (its arrays are [B][dof])");
-    if (const char* msg = pik::make_params_k(p, pk)) return fail(PIKAMD_EINVAL, "%s", msg);
-    if (B > 0 && any_null)
-        return fail(PIKAMD_EINVAL, "pikamd_search_global_batch: goal_pos_quat, seed, solution and status must not be NULL");
-    return 0;
-}
 
 // The attempts of one call on `stream` (device pointers in `r`: B, K, user_guess, the key, the primary outputs and
 // all_*; goal / seed apart).  sync_between: the host-pointer entry point -- the open count is read back behind every
@@ -1871,29 +1807,18 @@ int32_t pikamd_search_global_batch_device(pikamd_solver* s, const pikamd_params*
                                           int32_t max_attempts, double* d_solution, int32_t* d_status,
                                           double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
                                           double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot) {
+    const SearchArrays d = {d_goal_pos_quat, d_seed,  d_initial_guess, d_solution,     d_status,
+                            d_final_cost,    d_stats, d_attempts,      d_all_solution, d_all_status};
     pik::ParamsK pk;
-    if (int rc = check_search_global(s, p, B, max_attempts, !d_goal_pos_quat || !d_seed || !d_solution || !d_status, pk))
-        return rc;
+    if (int rc = check_call(SEARCH_GLOBAL, s, p, B, max_attempts, d.required_null(), pk)) return rc;
     if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
     if (B == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::RestartOps* ops = restart_ops_of(s, p, pk);
     if (!ops) return no_kernels(s->chain.dof);
     HIP_TRY(hipSetDevice(s->device));
-    pik::RestartArgs r = {};
-    r.B = B;
-    r.K = max_attempts;
-    r.user_guess = d_initial_guess ? d_initial_guess : d_seed;
-    r.rng_seed = rng_seed;
-    r.problem_offset = problem_offset;
-    r.solution = d_solution;
-    r.status = d_status;
-    r.cost = d_final_cost;
-    r.stats = d_stats;
-    r.attempts = d_attempts;
-    r.all_solution = d_all_solution;
-    r.all_status = d_all_status;
-    return run_search_global(s, p, pk, ops, r, d_goal_pos_quat, d_seed, (hipStream_t)stream, slot, false);
+    return run_search_global(s, p, pk, ops, restart_args(B, max_attempts, d, rng_seed, problem_offset), d.goal, d.seed,
+                             (hipStream_t)stream, slot, false);
 }
 
 int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int64_t B, const double* goal_pos_quat,
@@ -1901,70 +1826,20 @@ int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int
                                    int64_t problem_offset, int32_t max_attempts, double* solution, int32_t* status,
                                    double* final_cost, pikamd_stats* stats, int32_t* attempts, double* all_solution,
                                    int32_t* all_status) {
+    const SearchArrays h = {goal_pos_quat, seed, initial_guess, solution, status, final_cost, stats, attempts, all_solution, all_status};
     pik::ParamsK pk;
-    if (int rc = check_search_global(s, p, B, max_attempts, !goal_pos_quat || !seed || !solution || !status, pk)) return rc;
+    if (int rc = check_call(SEARCH_GLOBAL, s, p, B, max_attempts, h.required_null(), pk)) return rc;
     if (B == 0) return 0;
     if (int rc = maybe_self_test(s, p)) return rc; // (the GLOBAL-mode kernel set, as pikamd_solve_batch)
     const pik::RestartOps* ops = restart_ops_of(s, p, pk);
     if (!ops) return no_kernels(s->chain.dof);
-    // staged like pikamd_search_batch, through the synchronous entry points' job
-    const int job = PIKAMD_MAX_HOST_JOBS - 1;
-    pik::HostJob& J = s->jobs[job];
-    if (J.pending) return fail(PIKAMD_EINVAL, "job %d is still in flight: call pikamd_wait first", job);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!J.stream) HIP_TRY(hipStreamCreateWithFlags(&J.stream, hipStreamNonBlocking));
-    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, n = (size_t)B, rows = n * (size_t)max_attempts;
-    const size_t off_goal = 0, off_seed = off_goal + sizeof(double) * g7 * n, off_guess = off_seed + sizeof(double) * d * n;
-    const size_t in_bytes = off_guess + (initial_guess ? sizeof(double) * d * n : 0);
-    const size_t off_solution = in_bytes, off_cost = off_solution + sizeof(double) * d * n;
-    const size_t off_stats = off_cost + sizeof(double) * n, off_status = off_stats + sizeof(pikamd_stats) * n;
-    const size_t off_attempts = off_status + align8(sizeof(int32_t) * n);
-    const size_t off_all_solution = off_attempts + align8(sizeof(int32_t) * n);
-    const size_t off_all_status = off_all_solution + (all_solution ? sizeof(double) * d * rows : 0);
-    const size_t total = off_all_status + (all_status ? align8(sizeof(int32_t) * rows) : 0);
-    if (int rc = J.dev.ensure(total)) return rc;
-    if (int rc = J.host.ensure(total)) return rc;
-    char* hb = (char*)J.host.p;
-    char* db = (char*)J.dev.p;
-    pik::RestartArgs r = {};
-    r.B = B;
-    r.K = max_attempts;
-    r.user_guess = initial_guess ? (const double*)(db + off_guess) : (const double*)(db + off_seed);
-    r.rng_seed = rng_seed;
-    r.problem_offset = problem_offset;
-    r.solution = (double*)(db + off_solution);
-    r.status = (int*)(db + off_status);
-    r.cost = (double*)(db + off_cost);
-    r.stats = (void*)(db + off_stats);
-    r.attempts = (int*)(db + off_attempts);
-    r.all_solution = all_solution ? (double*)(db + off_all_solution) : nullptr;
-    r.all_status = all_status ? (int32_t*)(db + off_all_status) : nullptr;
-    const int slot = pik::N_DEVICE_SLOTS + job;
-    std::memcpy(hb + off_goal, goal_pos_quat, sizeof(double) * g7 * n);
-    std::memcpy(hb + off_seed, seed, sizeof(double) * d * n);
-    if (initial_guess) std::memcpy(hb + off_guess, initial_guess, sizeof(double) * d * n);
-    HIP_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, J.stream));
-    // (work of this call may be in flight from here on: the stream is drained before an error is returned)
-    if (int rc = run_search_global(s, p, pk, ops, r, (const double*)(db + off_goal), (const double*)(db + off_seed),
-                                   J.stream, slot, true)) {
-        (void)hipStreamSynchronize(J.stream);
-        return rc;
-    }
-    {
-        hipError_t e = hipMemcpyAsync(hb + in_bytes, db + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, J.stream);
-        const hipError_t e2 = hipStreamSynchronize(J.stream);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess)
-            return fail(PIKAMD_EHIP, "pikamd_search_global_batch: %s (its results are lost)", hipGetErrorString(e));
-    }
-    std::memcpy(solution, hb + off_solution, sizeof(double) * d * n);
-    std::memcpy(status, hb + off_status, sizeof(int32_t) * n);
-    if (final_cost) std::memcpy(final_cost, hb + off_cost, sizeof(double) * n);
-    if (stats) std::memcpy(stats, hb + off_stats, sizeof(pikamd_stats) * n);
-    if (attempts) std::memcpy(attempts, hb + off_attempts, sizeof(int32_t) * n);
-    if (all_solution) std::memcpy(all_solution, hb + off_all_solution, sizeof(double) * d * rows);
-    if (all_status) std::memcpy(all_status, hb + off_all_status, sizeof(int32_t) * rows);
-    return 0;
+    Staging st(s, SEARCH_GLOBAL.name);
+    if (int rc = st.begin()) return rc;
+    SearchArrays d;
+    if (int rc = stage_search(st, s, h, B, max_attempts, d)) return rc;
+    if (int rc = st.upload()) return rc;
+    return st.finish(run_search_global(s, p, pk, ops, restart_args(B, max_attempts, d, rng_seed, problem_offset), d.goal,
+                                       d.seed, st.stream(), Staging::SLOT, true));
 }
 
 } // extern "C"

@@ -4,17 +4,11 @@
 #ifndef PIK_INST_D
 #error "compile with -DPIK_INST_D=<dof>"
 #endif
-#define PIK_CAT2(a, b) a##b
-#define PIK_CAT(a, b) PIK_CAT2(a, b)
-
 #if defined(PIK_INST_STUB)
 #include "pik_path_ops.hpp"
-namespace pik {
-const PathOps* PIK_CAT(path_ops_d, PIK_INST_D)() { return nullptr; }
-} // namespace pik
 #else
 #include "pik_path.hpp"
-namespace pik {
-const PathOps* PIK_CAT(path_ops_d, PIK_INST_D)() { return make_path_ops<PIK_INST_D>(); }
-} // namespace pik
 #endif
+namespace pik {
+PIK_DEFINE_OPS(PathOps, path)
+} // namespace pik

@@ -3,6 +3,7 @@
 // the launch (launch_paths) and pikamd_path_kernel_name.  No device code here; not read by pik_inst.hip.
 #pragma once
 
+#include "pik_dofs.hpp"
 #include "pik_solver.hpp"
 
 namespace pik {
@@ -26,23 +27,7 @@ struct PathOps {
     int (*solve)(pikamd_solver*, const ParamsK&, const PathArgs&, hipStream_t, int slot);
 };
 
-#define PIK_DECLARE_PATH_OPS(N) const PathOps* path_ops_d##N();
-PIK_DECLARE_PATH_OPS(1) PIK_DECLARE_PATH_OPS(2) PIK_DECLARE_PATH_OPS(3) PIK_DECLARE_PATH_OPS(4)
-PIK_DECLARE_PATH_OPS(5) PIK_DECLARE_PATH_OPS(6) PIK_DECLARE_PATH_OPS(7) PIK_DECLARE_PATH_OPS(8)
-PIK_DECLARE_PATH_OPS(9) PIK_DECLARE_PATH_OPS(10) PIK_DECLARE_PATH_OPS(11) PIK_DECLARE_PATH_OPS(12)
-PIK_DECLARE_PATH_OPS(13) PIK_DECLARE_PATH_OPS(14) PIK_DECLARE_PATH_OPS(15) PIK_DECLARE_PATH_OPS(16)
-#undef PIK_DECLARE_PATH_OPS
-
-inline const PathOps* path_ops(int dof) {
-    switch (dof) {
-#define PIK_PATH_CASE(N) case N: return path_ops_d##N();
-        PIK_PATH_CASE(1) PIK_PATH_CASE(2) PIK_PATH_CASE(3) PIK_PATH_CASE(4) PIK_PATH_CASE(5) PIK_PATH_CASE(6)
-        PIK_PATH_CASE(7) PIK_PATH_CASE(8) PIK_PATH_CASE(9) PIK_PATH_CASE(10) PIK_PATH_CASE(11) PIK_PATH_CASE(12)
-        PIK_PATH_CASE(13) PIK_PATH_CASE(14) PIK_PATH_CASE(15) PIK_PATH_CASE(16)
-#undef PIK_PATH_CASE
-        default: return nullptr;
-    }
-}
+PIK_DECLARE_OPS_FAMILY(PathOps, path) // path_ops_d<N>(), path_ops(dof)
 
 // Lanes per path of a call of P paths: the rule launch_solve has for the problems of a local-mode call
 // (pik_launch.hpp).  Exact flavours, one tip frame: the team kernels with 16 (or 4) lanes as long as every path gets

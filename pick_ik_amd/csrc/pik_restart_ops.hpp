@@ -49,24 +49,7 @@ struct RestartOps {
                    const int* list, long long n_hint, hipStream_t, int slot);
 };
 
-#define PIK_DECLARE_RESTART_OPS(N) const RestartOps* restart_ops_d##N();
-PIK_DECLARE_RESTART_OPS(1) PIK_DECLARE_RESTART_OPS(2) PIK_DECLARE_RESTART_OPS(3) PIK_DECLARE_RESTART_OPS(4)
-PIK_DECLARE_RESTART_OPS(5) PIK_DECLARE_RESTART_OPS(6) PIK_DECLARE_RESTART_OPS(7) PIK_DECLARE_RESTART_OPS(8)
-PIK_DECLARE_RESTART_OPS(9) PIK_DECLARE_RESTART_OPS(10) PIK_DECLARE_RESTART_OPS(11) PIK_DECLARE_RESTART_OPS(12)
-PIK_DECLARE_RESTART_OPS(13) PIK_DECLARE_RESTART_OPS(14) PIK_DECLARE_RESTART_OPS(15) PIK_DECLARE_RESTART_OPS(16)
-#undef PIK_DECLARE_RESTART_OPS
-
-inline const RestartOps* restart_ops(int dof) {
-    switch (dof) {
-#define PIK_RESTART_CASE(N) case N: return restart_ops_d##N();
-        PIK_RESTART_CASE(1) PIK_RESTART_CASE(2) PIK_RESTART_CASE(3) PIK_RESTART_CASE(4) PIK_RESTART_CASE(5)
-        PIK_RESTART_CASE(6) PIK_RESTART_CASE(7) PIK_RESTART_CASE(8) PIK_RESTART_CASE(9) PIK_RESTART_CASE(10)
-        PIK_RESTART_CASE(11) PIK_RESTART_CASE(12) PIK_RESTART_CASE(13) PIK_RESTART_CASE(14) PIK_RESTART_CASE(15)
-        PIK_RESTART_CASE(16)
-#undef PIK_RESTART_CASE
-        default: return nullptr;
-    }
-}
+PIK_DECLARE_OPS_FAMILY(RestartOps, restart) // restart_ops_d<N>(), restart_ops(dof)
 
 // rng_seed_a of the header: attempt a's seed is the caller's with a added to its HIGH word (mod 2^64)
 inline unsigned long long restart_attempt_seed(unsigned long long rng_seed, int a) {

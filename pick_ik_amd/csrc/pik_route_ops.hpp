@@ -4,6 +4,7 @@
 // pik_inst.hip.
 #pragma once
 
+#include "pik_dofs.hpp"
 #include "pik_solver.hpp"
 
 namespace pik {
@@ -49,23 +50,7 @@ struct RouteOps {
                  unsigned long long rng_seed, hipStream_t, int slot, RouteCtx* ctx);
 };
 
-#define PIK_DECLARE_ROUTE_OPS(N) const RouteOps* route_ops_d##N();
-PIK_DECLARE_ROUTE_OPS(1) PIK_DECLARE_ROUTE_OPS(2) PIK_DECLARE_ROUTE_OPS(3) PIK_DECLARE_ROUTE_OPS(4)
-PIK_DECLARE_ROUTE_OPS(5) PIK_DECLARE_ROUTE_OPS(6) PIK_DECLARE_ROUTE_OPS(7) PIK_DECLARE_ROUTE_OPS(8)
-PIK_DECLARE_ROUTE_OPS(9) PIK_DECLARE_ROUTE_OPS(10) PIK_DECLARE_ROUTE_OPS(11) PIK_DECLARE_ROUTE_OPS(12)
-PIK_DECLARE_ROUTE_OPS(13) PIK_DECLARE_ROUTE_OPS(14) PIK_DECLARE_ROUTE_OPS(15) PIK_DECLARE_ROUTE_OPS(16)
-#undef PIK_DECLARE_ROUTE_OPS
-
-inline const RouteOps* route_ops(int dof) {
-    switch (dof) {
-#define PIK_ROUTE_CASE(N) case N: return route_ops_d##N();
-        PIK_ROUTE_CASE(1) PIK_ROUTE_CASE(2) PIK_ROUTE_CASE(3) PIK_ROUTE_CASE(4) PIK_ROUTE_CASE(5) PIK_ROUTE_CASE(6)
-        PIK_ROUTE_CASE(7) PIK_ROUTE_CASE(8) PIK_ROUTE_CASE(9) PIK_ROUTE_CASE(10) PIK_ROUTE_CASE(11) PIK_ROUTE_CASE(12)
-        PIK_ROUTE_CASE(13) PIK_ROUTE_CASE(14) PIK_ROUTE_CASE(15) PIK_ROUTE_CASE(16)
-#undef PIK_ROUTE_CASE
-        default: return nullptr;
-    }
-}
+PIK_DECLARE_OPS_FAMILY(RouteOps, route) // route_ops_d<N>(), route_ops(dof)
 
 // option device_regime: "1" (or "", the default) / "0"; anything else is refused
 inline bool parse_device_regime(const char* value, int* out) {

@@ -39,24 +39,7 @@ struct SearchOps {
     int (*solve)(pikamd_solver*, const ParamsK&, const SearchArgs&, hipStream_t, int slot);
 };
 
-#define PIK_DECLARE_SEARCH_OPS(N) const SearchOps* search_ops_d##N();
-PIK_DECLARE_SEARCH_OPS(1) PIK_DECLARE_SEARCH_OPS(2) PIK_DECLARE_SEARCH_OPS(3) PIK_DECLARE_SEARCH_OPS(4)
-PIK_DECLARE_SEARCH_OPS(5) PIK_DECLARE_SEARCH_OPS(6) PIK_DECLARE_SEARCH_OPS(7) PIK_DECLARE_SEARCH_OPS(8)
-PIK_DECLARE_SEARCH_OPS(9) PIK_DECLARE_SEARCH_OPS(10) PIK_DECLARE_SEARCH_OPS(11) PIK_DECLARE_SEARCH_OPS(12)
-PIK_DECLARE_SEARCH_OPS(13) PIK_DECLARE_SEARCH_OPS(14) PIK_DECLARE_SEARCH_OPS(15) PIK_DECLARE_SEARCH_OPS(16)
-#undef PIK_DECLARE_SEARCH_OPS
-
-inline const SearchOps* search_ops(int dof) {
-    switch (dof) {
-#define PIK_SEARCH_CASE(N) case N: return search_ops_d##N();
-        PIK_SEARCH_CASE(1) PIK_SEARCH_CASE(2) PIK_SEARCH_CASE(3) PIK_SEARCH_CASE(4) PIK_SEARCH_CASE(5)
-        PIK_SEARCH_CASE(6) PIK_SEARCH_CASE(7) PIK_SEARCH_CASE(8) PIK_SEARCH_CASE(9) PIK_SEARCH_CASE(10)
-        PIK_SEARCH_CASE(11) PIK_SEARCH_CASE(12) PIK_SEARCH_CASE(13) PIK_SEARCH_CASE(14) PIK_SEARCH_CASE(15)
-        PIK_SEARCH_CASE(16)
-#undef PIK_SEARCH_CASE
-        default: return nullptr;
-    }
-}
+PIK_DECLARE_OPS_FAMILY(SearchOps, search) // search_ops_d<N>(), search_ops(dof)
 
 // option search_schedule
 constexpr int SEARCH_ADAPTIVE = 0, SEARCH_SEQUENTIAL = 1, SEARCH_PARALLEL = 2;

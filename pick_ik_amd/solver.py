@@ -693,7 +693,51 @@ class Solver:
         self._env_options()
         return self._L.pikamd_path_kernel_name(self._h, C.byref(params), P).decode()
 
-    # ---- local IK with random restarts ----------------------------------------------------
+    # ---- IK with random restarts: local mode (search_batch), the memetic solver (search_global_batch) ----
+    def _search(self, entry, params, goal_pos_quat, seed, max_attempts, rng_seed, problem_offset, initial_guess, all_attempts):
+        """search_batch / search_global_batch; entry: the name of the library's entry point"""
+        self._env_options()
+        goal = _f64(goal_pos_quat)
+        if goal.ndim < 2 or goal.size != goal.shape[0] * 7 * self.n_tips:
+            raise ValueError(f"goal_pos_quat: expected [B]{[7] if self.n_tips == 1 else [self.n_tips, 7]}, "
+                             f"got {list(goal.shape)}")
+        B = goal.shape[0]
+        seed = _f64(seed)
+        if seed.shape != (B, self.dof):
+            raise ValueError(f"seed: expected [{B}][{self.dof}], got {list(seed.shape)}")
+        guess = None
+        if initial_guess is not None:
+            guess = _f64(initial_guess)
+            if guess.shape != (B, self.dof):
+                raise ValueError(f"initial_guess: expected [{B}][{self.dof}], got {list(guess.shape)}")
+        K = int(max_attempts)
+        if not 1 <= K <= MAX_ATTEMPTS:
+            raise ValueError(f"max_attempts: expected 1..{MAX_ATTEMPTS}, got {max_attempts}")
+        sol = np.empty((B, self.dof))
+        status = np.empty(B, dtype=np.int32)
+        cost = np.empty(B)
+        stats = np.zeros(B, dtype=STATS_DTYPE)
+        attempts = np.empty(B, dtype=np.int32)
+        all_sol = np.empty((B, K, self.dof)) if all_attempts else None
+        all_st = np.empty((B, K), dtype=np.int32) if all_attempts else None
+        # (C.c_uint64 takes any int modulo 2^64: a seed with the attempt in its high word may have wrapped)
+        self._chk(getattr(self._L, entry)(
+            self._h, C.byref(params), B, _dp(goal), _dp(seed), None if guess is None else _dp(guess), C.c_uint64(rng_seed),
+            problem_offset, K, _dp(sol), _ip(status), _dp(cost), stats.ctypes.data_as(C.c_void_p), _ip(attempts),
+            None if all_sol is None else _dp(all_sol), None if all_st is None else _ip(all_st)))
+        if all_attempts:
+            return sol, status, cost, stats, attempts, all_sol, all_st
+        return sol, status, cost, stats, attempts
+
+    def _search_device(self, entry, params, B, d_goal, d_seed, max_attempts, d_solution, d_status, d_initial_guess, d_cost,
+                       d_stats, d_attempts, d_all_solution, d_all_status, rng_seed, problem_offset, stream, slot):
+        """search_batch_device / search_global_batch_device; entry: the name of the library's entry point"""
+        self._env_options()
+        self._chk(getattr(self._L, entry)(
+            self._h, C.byref(params), B, d_goal or None, d_seed or None, d_initial_guess or None, C.c_uint64(rng_seed),
+            problem_offset, max_attempts, d_solution or None, d_status or None, d_cost or None, d_stats or None,
+            d_attempts or None, d_all_solution or None, d_all_status or None, stream or None, slot))
+
     def search_batch(self, params: Params, goal_pos_quat, seed, max_attempts: int, rng_seed: int = 0,
                      problem_offset: int = 0, initial_guess=None, all_attempts: bool = False):
         """pikamd_search_batch: local mode (params.mode = 1) with up to max_attempts (1..MAX_ATTEMPTS) attempts per
@@ -702,37 +746,8 @@ class Solver:
         all_attempts, (all_solution [B][max_attempts][dof], all_status [B][max_attempts]) behind them: every attempt
         of every problem, run without an early exit.  The result is what the loop of solve_batch calls in
         include/pick_ik_amd.h returns, bit for bit."""
-        self._env_options()
-        goal = _f64(goal_pos_quat)
-        if goal.ndim < 2 or goal.size != goal.shape[0] * 7 * self.n_tips:
-            raise ValueError(f"goal_pos_quat: expected [B]{[7] if self.n_tips == 1 else [self.n_tips, 7]}, "
-                             f"got {list(goal.shape)}")
-        B = goal.shape[0]
-        seed = _f64(seed)
-        if seed.shape != (B, self.dof):
-            raise ValueError(f"seed: expected [{B}][{self.dof}], got {list(seed.shape)}")
-        guess = None
-        if initial_guess is not None:
-            guess = _f64(initial_guess)
-            if guess.shape != (B, self.dof):
-                raise ValueError(f"initial_guess: expected [{B}][{self.dof}], got {list(guess.shape)}")
-        K = int(max_attempts)
-        if not 1 <= K <= MAX_ATTEMPTS:
-            raise ValueError(f"max_attempts: expected 1..{MAX_ATTEMPTS}, got {max_attempts}")
-        sol = np.empty((B, self.dof))
-        status = np.empty(B, dtype=np.int32)
-        cost = np.empty(B)
-        stats = np.zeros(B, dtype=STATS_DTYPE)
-        attempts = np.empty(B, dtype=np.int32)
-        all_sol = np.empty((B, K, self.dof)) if all_attempts else None
-        all_st = np.empty((B, K), dtype=np.int32) if all_attempts else None
-        self._chk(self._L.pikamd_search_batch(
-            self._h, C.byref(params), B, _dp(goal), _dp(seed), None if guess is None else _dp(guess),
-            C.c_uint64(rng_seed), problem_offset, K, _dp(sol), _ip(status), _dp(cost), stats.ctypes.data_as(C.c_void_p),
-            _ip(attempts), None if all_sol is None else _dp(all_sol), None if all_st is None else _ip(all_st)))
-        if all_attempts:
-            return sol, status, cost, stats, attempts, all_sol, all_st
-        return sol, status, cost, stats, attempts
+        return self._search("pikamd_search_batch", params, goal_pos_quat, seed, max_attempts, rng_seed, problem_offset,
+                            initial_guess, all_attempts)
 
     def search_batch_device(self, params: Params, B: int, d_goal: int, d_seed: int, max_attempts: int, d_solution: int,
                             d_status: int, d_initial_guess: int = 0, d_cost: int = 0, d_stats: int = 0,
@@ -740,51 +755,18 @@ class Solver:
                             problem_offset: int = 0, stream: int = 0, slot: int = 0):
         """Enqueue a restart search on HBM-resident buffers (raw device addresses); returns immediately -- the caller
         synchronises the stream."""
-        self._env_options()
-        self._chk(self._L.pikamd_search_batch_device(
-            self._h, C.byref(params), B, d_goal or None, d_seed or None, d_initial_guess or None, C.c_uint64(rng_seed),
-            problem_offset, max_attempts, d_solution or None, d_status or None, d_cost or None, d_stats or None,
-            d_attempts or None, d_all_solution or None, d_all_status or None, stream or None, slot))
+        self._search_device("pikamd_search_batch_device", params, B, d_goal, d_seed, max_attempts, d_solution, d_status,
+                            d_initial_guess, d_cost, d_stats, d_attempts, d_all_solution, d_all_status, rng_seed,
+                            problem_offset, stream, slot)
 
-    # ---- memetic IK with random restarts ---------------------------------------------------
     def search_global_batch(self, params: Params, goal_pos_quat, seed, max_attempts: int, rng_seed: int = 0,
                             problem_offset: int = 0, initial_guess=None, all_attempts: bool = False):
         """pikamd_search_global_batch: global mode (params.mode = 0) with up to max_attempts (1..MAX_ATTEMPTS) attempts
         per problem; attempt a solves with rng_seed + (a << 32), every attempt after a failure from a random valid
         configuration keyed by (rng_seed, problem_offset + b, attempt).  Returns what search_batch returns; the result is
         what the loop of one-record solve_batches calls in include/pick_ik_amd.h returns, bit for bit."""
-        self._env_options()
-        goal = _f64(goal_pos_quat)
-        if goal.ndim < 2 or goal.size != goal.shape[0] * 7 * self.n_tips:
-            raise ValueError(f"goal_pos_quat: expected [B]{[7] if self.n_tips == 1 else [self.n_tips, 7]}, "
-                             f"got {list(goal.shape)}")
-        B = goal.shape[0]
-        seed = _f64(seed)
-        if seed.shape != (B, self.dof):
-            raise ValueError(f"seed: expected [{B}][{self.dof}], got {list(seed.shape)}")
-        guess = None
-        if initial_guess is not None:
-            guess = _f64(initial_guess)
-            if guess.shape != (B, self.dof):
-                raise ValueError(f"initial_guess: expected [{B}][{self.dof}], got {list(guess.shape)}")
-        K = int(max_attempts)
-        if not 1 <= K <= MAX_ATTEMPTS:
-            raise ValueError(f"max_attempts: expected 1..{MAX_ATTEMPTS}, got {max_attempts}")
-        sol = np.empty((B, self.dof))
-        status = np.empty(B, dtype=np.int32)
-        cost = np.empty(B)
-        stats = np.zeros(B, dtype=STATS_DTYPE)
-        attempts = np.empty(B, dtype=np.int32)
-        all_sol = np.empty((B, K, self.dof)) if all_attempts else None
-        all_st = np.empty((B, K), dtype=np.int32) if all_attempts else None
-        self._chk(self._L.pikamd_search_global_batch(
-            self._h, C.byref(params), B, _dp(goal), _dp(seed), None if guess is None else _dp(guess),
-            C.c_uint64(rng_seed % (1 << 64)), problem_offset, K, _dp(sol), _ip(status), _dp(cost),
-            stats.ctypes.data_as(C.c_void_p), _ip(attempts), None if all_sol is None else _dp(all_sol),
-            None if all_st is None else _ip(all_st)))
-        if all_attempts:
-            return sol, status, cost, stats, attempts, all_sol, all_st
-        return sol, status, cost, stats, attempts
+        return self._search("pikamd_search_global_batch", params, goal_pos_quat, seed, max_attempts, rng_seed, problem_offset,
+                            initial_guess, all_attempts)
 
     def search_global_batch_device(self, params: Params, B: int, d_goal: int, d_seed: int, max_attempts: int,
                                    d_solution: int, d_status: int, d_initial_guess: int = 0, d_cost: int = 0,
@@ -792,12 +774,9 @@ class Solver:
                                    rng_seed: int = 0, problem_offset: int = 0, stream: int = 0, slot: int = 0):
         """Enqueue a global-mode restart search on HBM-resident buffers (raw device addresses): all max_attempts
         attempts; returns immediately -- the caller synchronises the stream."""
-        self._env_options()
-        self._chk(self._L.pikamd_search_global_batch_device(
-            self._h, C.byref(params), B, d_goal or None, d_seed or None, d_initial_guess or None,
-            C.c_uint64(rng_seed % (1 << 64)), problem_offset, max_attempts, d_solution or None, d_status or None,
-            d_cost or None, d_stats or None, d_attempts or None, d_all_solution or None, d_all_status or None,
-            stream or None, slot))
+        self._search_device("pikamd_search_global_batch_device", params, B, d_goal, d_seed, max_attempts, d_solution, d_status,
+                            d_initial_guess, d_cost, d_stats, d_attempts, d_all_solution, d_all_status, rng_seed,
+                            problem_offset, stream, slot)
 
     def search_kernel_name(self, params: Params, B: int, max_attempts: int):
         """(the kernel search_batch launches for B problems of max_attempts attempts, attempts in flight per problem:

@@ -19,7 +19,7 @@ def test_route_objects_hold_the_router_kernel_and_no_memetic_kernel():
     from pick_ik_amd import kernel_resources as KR
     assert set(B.ROUTE_FLAVOURS) == set(FLAVOURS)
     for fl, ns in FLAVOURS.items():
-        objs = B._route_objects(fl)
+        objs = B.family_objects("pik_route_inst.hip", fl)
         assert len(objs) == 16 and all(o[1] == "pik_route_inst.hip" for o in objs)
         for d, o in zip(B.DOFS, objs):
             if not os.path.exists(o[0] + ".res"):
@@ -35,9 +35,11 @@ def test_route_objects_hold_the_router_kernel_and_no_memetic_kernel():
 def test_route_objects_are_compiled_with_their_flavour_s_flags():
     from pick_ik_amd import build as B
     for fl in FLAVOURS:
-        inst = {"fast": B._objects(False)[2:], "exact": B._exact_objects(), "common": B._common_objects(),
-                "common_goals": B._common_objects(True)}[fl]
-        for a, b in zip(inst, B._route_objects(fl)):
+        inst = B.family_objects("pik_inst.hip", fl)
+        assert inst == {"fast": B.library_objects(False)[2:18], "exact": B.library_objects(False)[18:34],
+                        "common": B.library_objects(False)[34:50], "common_goals": B.library_objects(False)[50:66]}[fl]
+        assert len(inst) == 16 and all(o[1] == "pik_inst.hip" for o in inst)
+        for a, b in zip(inst, B.family_objects("pik_route_inst.hip", fl)):
             strip = lambda cmd: [x for x in cmd if not x.endswith((".o", ".hip"))]  # noqa: E731
             assert strip(B._cmd(*a, False)) == strip(B._cmd(*b, False)), (fl, a[0])
     assert "pik_route.hpp" not in {os.path.basename(f) for f in B._deps("pik_inst.hip", True)}

@@ -14,6 +14,7 @@ import pytest
 
 import pick_ik_amd as pk
 from pick_ik_amd import robots
+from tests import abi_calls as A
 from tests import path_reference as PR
 from tests.test_mimic_cpu import CASES, with_mimic
 
@@ -258,6 +259,23 @@ def test_edges_and_refusals(O):
             s.solve_paths(p, goals, start)
         s.set_option("joint_layout", "aos")
         same(s.solve_paths(p, goals, start), (sol, st, cost, stats, reached), "after the refusals")
+    finally:
+        s.close()
+
+
+def test_every_optional_array_may_be_absent(O):
+    """P = 3 paths of W = 3 waypoints (odd row counts: the int32 arrays end off an 8-byte boundary): the call with
+    every optional array, then with each one NULL in turn -- every array still given is the full call's, bit for bit
+    (the step limit given is "no limit": leaving it out changes no answer)"""
+    ch = robots.panda()
+    s = pk.Solver(ch, device=0)
+    try:
+        goals, start = PR.straight_lines(ch, s.fk, P=3, W=3)
+        p = pk.default_params(mode=1)
+        full = A.check_optional_arrays(
+            lambda a: A.solve_paths(s._L, s._h, p, 3, 3, a), lambda: A.path_arrays(s, goals, start, np.full(ch.dof, -1.0)),
+            ("final_cost", "stats", "reached", "max_joint_step"), A.PATH_OUTPUTS)
+        same([full[k] for k in A.PATH_OUTPUTS], s.solve_paths(p, goals, start), "binding")
     finally:
         s.close()
 

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import pick_ik_amd as pk
+from tests import abi_calls as A
 from tests import search_reference as SR
 
 pytestmark = pytest.mark.gpu
@@ -278,6 +279,24 @@ def test_edges_and_refusals(O):
             s.search_batch(p, goals, seed, K)
         s.set_option("joint_layout", "aos")
         same(s.search_batch(p, goals, seed, K), ref, "after the refusals")
+    finally:
+        s.close()
+
+
+def test_every_optional_array_may_be_absent(O):
+    """B = 3 problems of K = 3 attempts (odd row counts: the int32 arrays end off an 8-byte boundary): the call with
+    every optional array, then with each one NULL in turn -- every array still given is the full call's, bit for bit"""
+    s = pk.Solver(SR.CASES["panda"][0](), device=0)
+    try:
+        ch, goals, seed, _ = SR.fixture("panda", lambda _: s.fk, 3)
+        goals[2, 0] += 5.0  # (out of reach: every attempt of this problem runs)
+        p = pk.default_params(mode=1)
+        full = A.check_optional_arrays(
+            lambda a: A.search(s._L, s._h, p, 3, 3, a, rng_seed=3), lambda: A.search_arrays(s, goals, seed, seed.copy(), 3),
+            ("final_cost", "stats", "attempts", "all_solution", "all_status", "initial_guess"),
+            A.SEARCH_OUTPUTS)
+        same([full[k] for k in A.SEARCH_OUTPUTS], s.search_batch(p, goals, seed, 3, rng_seed=3, all_attempts=True), "binding")
+        assert full["attempts"][2] == 3 and full["status"][2] <= 0
     finally:
         s.close()
 

@@ -18,6 +18,7 @@ import pytest
 
 import pick_ik_amd as pk
 from tests import search_global_reference as GR
+from tests import abi_calls as A
 from tests import search_reference as SR
 
 pytestmark = pytest.mark.gpu
@@ -280,6 +281,22 @@ def test_edges_and_refusals(O):
             same(s.solve_batch(p, goals, seed, rng_seed=9), fresh.solve_batch(p, goals, seed, rng_seed=9), "solve_batch")
         finally:
             fresh.close()
+    finally:
+        s.close()
+
+
+def test_every_optional_array_may_be_absent(O):
+    """B = 3 problems of K = 3 attempts (odd row counts: the int32 arrays end off an 8-byte boundary): the call with
+    every optional array, then with each one NULL in turn -- every array still given is the full call's, bit for bit"""
+    s, ch, goals, seed, p = handle_fixture("panda", n=3, far=1)
+    try:
+        full = A.check_optional_arrays(
+            lambda a: A.search(s._L, s._h, p, 3, 3, a, global_mode=True, rng_seed=3),
+            lambda: A.search_arrays(s, goals, seed, seed.copy(), 3),
+            ("final_cost", "stats", "attempts", "all_solution", "all_status", "initial_guess"),
+            A.SEARCH_OUTPUTS)
+        same([full[k] for k in A.SEARCH_OUTPUTS], s.search_global_batch(p, goals, seed, 3, rng_seed=3, all_attempts=True), "binding")
+        assert full["attempts"][2] == 3 and full["status"][2] <= 0
     finally:
         s.close()
 

@@ -148,7 +148,8 @@ def test_restart_launcher_leaves_the_existing_translation_units_alone():
     for src in ("pik_inst.hip", "pik_path_inst.hip", "pik_search_inst.hip", "pik_route_inst.hip"):
         for f in Bd._deps(src, True):
             assert "pik_restart" not in os.path.basename(f), (src, f)
-    objs = Bd._all_restart_objects(False) + Bd._all_restart_objects(True)
+    objs = [o for strict in (False, True) for o in Bd.library_objects(strict) if "pik_restart" in o[0]]
+    assert objs == [o for fl in Bd.ROUTE_FLAVOURS + ("strict",) for o in Bd.family_objects("pik_restart_inst.hip", fl)]
     assert len(objs) == 16 * 5 and {o[1] for o in objs} == {"pik_restart_inst.hip"}
 
 
