@@ -501,6 +501,9 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
  *       init[b] = draw(b, 0, init[b])                                                     a NaN is invalid)
  *   for a in 0 .. max_attempts-1, for every b still open:
  *     (sol, st, cost, stats) = pikamd_solve_batch(local mode, goal[b], seed = seed[b], initial_guess = init[b])
+ *     if p->return_approximate_solution and a gate is set and st > 0 and not pass(sol, seed[b]):
+ *       st = PIKAMD_GATE_REFUSED; sol = seed[b]     (the approximate-solution gate below, :263-266; cost and stats stay
+ *                                                    what the solve returned, as for a refused path jump)
  *     solution[b] = sol; status[b] = st; final_cost[b] = cost; stats[b] += stats (field by field); attempts[b] = a + 1
  *     if st > 0: b is closed        (PIKAMD_SUCCESS or PIKAMD_APPROXIMATE: error_code SUCCESS ends the reference's loop)
  *     else: init[b] = draw(b, a + 1, init[b])
@@ -513,16 +516,18 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
  *     are the same doubles whatever serves the call.  An unbounded variable's draw is centred on the PREVIOUS
  *     attempt's start, as in the reference.
  *
- * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch.  With
- * return_approximate_solution set, attempt 0 always closes a problem (attempts == 1 everywhere).  A batch cut into
+ * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch (with a gate:
+ * pikamd_solve_batch + pikamd_gate_batch).  With return_approximate_solution set and NO gate on the handle, attempt 0
+ * always closes a problem (attempts == 1 everywhere); with a gate the restarts run for every refused answer.  A batch cut into
  * calls or shards with matching problem_offset gives the answers of one call.  The attempts of one problem are
  * independent computations, so the library may run them one after the other or side by side (option
  * search_schedule = adaptive | sequential | parallel: like the other scheduling options it changes no result).
  * all_solution / all_status: when either is given EVERY attempt of every problem is run and recorded, without an
  * early exit -- the rows behind a problem's winner are real results (several distinct IK solutions per target, for
- * a caller who collision-checks them); row a is what one pikamd_solve_batch from start a returns.  The primary
- * outputs are the loop's whether or not all_* is given.
- * The approximate-solution gate (src/pick_ik_plugin.cpp:219-267) and the solution callback stay with the caller.
+ * a caller who collision-checks them); row a is what one pikamd_solve_batch from start a returns, gated like the
+ * loop's.  The primary outputs are the loop's whether or not all_* is given.
+ * The approximate-solution gate (src/pick_ik_plugin.cpp:219-267) is the handle's (pikamd_set_approximate_gate below;
+ * none by default); the solution callback stays with the caller.
  * GLOBAL mode (mode 0) is refused here: pikamd_search_global_batch serves it.
  *   goal_pos_quat [B][n_tips][7], seed [B][dof], initial_guess [B][dof] (NULL = seed), solution [B][dof], status [B],
  *   final_cost [B] (may be NULL), stats [B] (may be NULL), attempts [B] (may be NULL),
@@ -562,6 +567,8 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
  *     (sol, st, cost, stats) = one pikamd_batch record {B = 1, goal[b], seed[b], initial_guess = init[b],
  *                                problem_offset = problem_offset + b} solved by pikamd_solve_batches in global mode
  *                                with rng_seed_a = rng_seed + ((uint64_t)a << 32)      (mod 2^64)
+ *     if p->return_approximate_solution and a gate is set and st > 0 and not pass(sol, seed[b]):
+ *       st = PIKAMD_GATE_REFUSED; sol = seed[b]                  (as in pikamd_search_batch; cost and stats stay)
  *     solution[b] = sol; status[b] = st; final_cost[b] = cost; stats[b] += stats (field by field); attempts[b] = a + 1
  *     if st > 0: b is closed     else: init[b] = draw(b, a + 1, init[b])
  *
@@ -573,15 +580,15 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
  * caller's seed unchanged.
  *
  * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch.  With
- * return_approximate_solution set, every problem closes at attempt 0.  A batch cut into calls or shards with matching
+ * return_approximate_solution set and no gate on the handle, every problem closes at attempt 0.  A batch cut into calls or shards with matching
  * problem_offset gives the answers of one call.  A restart starts from the re-drawn state, as the plugin shim's loop
  * does (the reference re-randomises init_state but keeps passing ik_seed_state; seed[b] stays the displacement
- * reference and what a failure returns).  The approximate-solution gate and the solution callback stay with the
- * caller.
+ * reference and what a failure returns).  The approximate-solution gate is the handle's
+ * (pikamd_set_approximate_gate); the solution callback stays with the caller.
  * all_solution [B][max_attempts][dof] / all_status [B][max_attempts]: when either is given EVERY attempt of every
  * problem runs, without an early exit; row a is what the one-record solve above returns from the start the loop's
- * draws give attempt a (every attempt counted as failed) with rng_seed_a.  The primary outputs are the loop's either
- * way.
+ * draws give attempt a (every attempt counted as failed) with rng_seed_a, gated like the loop's.  The primary outputs
+ * are the loop's either way.
  * Accepts what pikamd_solve_batch accepts in global mode: every kernel flavour, species, several tip frames,
  * floating and mimic chains, unbounded variables.  max_attempts is 1..PIKAMD_MAX_ATTEMPTS; B = 0 returns 0; NULL is
  * checked as in pikamd_search_batch (final_cost, stats, attempts, all_* may be NULL).  Not with the option
@@ -604,6 +611,37 @@ int32_t pikamd_search_global_batch_device(pikamd_solver* s, const pikamd_params*
                                           int32_t max_attempts, double* d_solution, int32_t* d_status,
                                           double* d_final_cost, pikamd_stats* d_stats, int32_t* d_attempts,
                                           double* d_all_solution, int32_t* d_all_status, void* stream, int32_t slot);
+/* ---- The approximate-solution gate ------------------------------------------------------------------
+ * With return_approximate_solution set the reference passes every answer of the solver through a gate
+ * (src/pick_ik_plugin.cpp:219-267): an answer it refuses becomes NO_IK_SOLUTION and the loop restarts from a random
+ * state.  The reference builds frame tests from its two approximate POSE thresholds and never uses them (:234-248); what
+ * it applies is make_is_solution_test_fn(frame_tests, goals, approximate_solution_cost_threshold) and then the
+ * joint-jump test.  That is the gate here; the two dead thresholds are not carried.
+ *
+ * pikamd_gate_batch: pass[i] = the reference's approx_solution_valid for candidate q[i], DEFINED by entry points above:
+ *   - is_solution[i] of pikamd_cost_batch(s, p', n, goal, seed, q, ...), p' = p with cost_threshold =
+ *     gate->cost_threshold when that is > 0, else p with the three joint-goal weights set to 0, AND
+ *   - for no j: fabs(q[i][j] - seed[i][j]) > gate->joint_threshold (tested only when gate->joint_threshold > 0).
+ * The comparisons are written exactly so: a NaN threshold limits nothing, a NaN difference does not trip the limit.
+ * Host pointers, arrays shaped as pikamd_cost_batch's, needs a device; n = 0 returns 0; a NULL gate or array and a
+ * handle with joint_layout = soa are refused (PIKAMD_EINVAL).  The evaluation is no cost_fn invocation of the solver:
+ * stats.cost_evals does not count it.
+ *
+ * pikamd_set_approximate_gate: the gate of pikamd_search_batch* and pikamd_search_global_batch* on this handle (the
+ * step in their loops above), applied only when p->return_approximate_solution is set (:222), to PIKAMD_SUCCESS as
+ * well as PIKAMD_APPROXIMATE -- a SUCCESS further than joint_threshold from the seed is refused, as in the reference.
+ * A failed attempt is not evaluated.  NULL = no gate, the default: every result is what it was.  Like
+ * pikamd_set_option: not concurrent with another call on the handle, read when a call is made.
+ * pikamd_solve_batch*, pikamd_solve_paths* and pikamd_solve_batch_host IGNORE the gate: they are the solver, the gate
+ * belongs to the loop around it. */
+typedef struct pikamd_gate {
+    double cost_threshold;  /* approximate_solution_cost_threshold; <= 0: no goal is tested (:240-242) */
+    double joint_threshold; /* approximate_solution_joint_threshold; not > 0: no limit (:253) */
+} pikamd_gate;
+#define PIKAMD_GATE_REFUSED (-1002) /* outside MoveItErrorCodes, like PIKAMD_PATH_JUMP; a MoveIt caller reports NO_IK_SOLUTION */
+int32_t pikamd_gate_batch(pikamd_solver* s, const pikamd_params* p, const pikamd_gate* gate, int64_t n,
+                          const double* goal_pos_quat, const double* seed, const double* q, int32_t* pass);
+int32_t pikamd_set_approximate_gate(pikamd_solver* s, const pikamd_gate* gate);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

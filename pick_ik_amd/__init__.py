@@ -5,5 +5,5 @@ include/pick_ik_amd.h), ``solver.py`` (ctypes mirror of the reference's solver i
 ``robots.py`` (serial-chain tables) and ``build.py``.
 """
 from . import robots  # noqa: F401
-from .solver import (APPROXIMATE, MAX_ATTEMPTS, NO_IK_SOLUTION, NOT_ATTEMPTED, PATH_JUMP, SUCCESS, Params,  # noqa: F401
-                     PickIkAmdError, Solver, default_params, ik_gradient, ik_memetic)
+from .solver import (APPROXIMATE, GATE_REFUSED, MAX_ATTEMPTS, NO_IK_SOLUTION, NOT_ATTEMPTED, PATH_JUMP, SUCCESS,  # noqa: F401
+                     Gate, Params, PickIkAmdError, Solver, default_params, ik_gradient, ik_memetic)

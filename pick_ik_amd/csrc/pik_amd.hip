@@ -97,6 +97,13 @@ struct SolverExt : pikamd_solver {
     int routed_passes[pik::N_SLOTS];
     // pikamd_search_global_batch*: per slot the starts, the rows of one attempt, the open flags and the open list
     pik::DevBuf restart_rows[pik::N_SLOTS];
+    // pikamd_set_approximate_gate: the gate of both search families, and per slot the parameters p' its evaluation
+    // reads on the device (gate_for_call)
+    bool gate_set = false;
+    pikamd_gate gate = {0.0, 0.0};
+    pik::DevBuf gate_params_dev; // [N_SLOTS] ParamsK, GATE_PARAMS_STRIDE apart
+    pik::ParamsK gate_params_host[pik::N_SLOTS];
+    bool gate_params_valid[pik::N_SLOTS] = {};
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -272,6 +279,34 @@ const pik::RestartOps* restart_ops_of(const pikamd_solver* s, const pikamd_param
 }
 
 size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
+
+// The approximate-solution gate of a search call on `slot`: on when the handle has one and the call sets
+// return_approximate_solution (src/pick_ik_plugin.cpp:222).  Then the slot's copy of p' (gate_params_k) is made current,
+// by upload_consts' rule: nothing is copied when the slot holds the same bytes, and when they change the slot's previous
+// stream is drained first and the copy is complete before the call goes on.
+constexpr size_t GATE_PARAMS_STRIDE = 256;
+static_assert(sizeof(pik::ParamsK) <= GATE_PARAMS_STRIDE, "gate parameters slot too small");
+int gate_for_call(pikamd_solver* s, const pik::ParamsK& pk, int slot, hipStream_t st, int* on, double* joint,
+                  const pik::ParamsK** dev) {
+    SolverExt* x = ext_of(s);
+    *on = (x->gate_set && pk.approx) ? 1 : 0;
+    *joint = x->gate.joint_threshold;
+    *dev = nullptr;
+    if (!*on) return 0;
+    if (int rc = x->gate_params_dev.ensure(GATE_PARAMS_STRIDE * (size_t)pik::N_SLOTS)) return rc;
+    char* d = (char*)x->gate_params_dev.p + GATE_PARAMS_STRIDE * (size_t)slot;
+    const pik::ParamsK want = pik::gate_params_k(pk, x->gate.cost_threshold);
+    if (!x->gate_params_valid[slot] || std::memcmp(&x->gate_params_host[slot], &want, sizeof want) != 0) {
+        if (s->consts_valid[slot]) HIP_TRY(hipStreamSynchronize(s->consts_stream[slot]));
+        x->gate_params_valid[slot] = false;
+        std::memcpy(&x->gate_params_host[slot], &want, sizeof want);
+        HIP_TRY(hipMemcpyAsync(d, &x->gate_params_host[slot], sizeof want, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        x->gate_params_valid[slot] = true;
+    }
+    *dev = reinterpret_cast<const pik::ParamsK*>(d);
+    return 0;
+}
 
 } // namespace
 
@@ -463,6 +498,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : s->slot_soa) b.release();
     for (auto& b : ext_of(s)->search_rows) b.release();
     for (auto& b : ext_of(s)->restart_rows) b.release();
+    ext_of(s)->gate_params_dev.release();
     for (auto& j : s->jobs) {
         j.dev.release();
         j.host.release();
@@ -1649,6 +1685,11 @@ int search_args(pikamd_solver* s, const pikamd_params* p, int slot, int64_t B, i
     return plan_search(s, p, slot, a, d.all_solution, d.all_status);
 }
 
+// the handle's gate into the arguments of a local-mode call (gate_for_call)
+int search_gate(pikamd_solver* s, const pik::ParamsK& pk, int slot, hipStream_t st, pik::SearchArgs& a) {
+    return gate_for_call(s, pk, slot, st, &a.gate, &a.gate_joint, &a.gate_params);
+}
+
 // ... and of a global-mode one (goal and seed apart: they go to the solver)
 pik::RestartArgs restart_args(int64_t B, int32_t K, const SearchArrays& d, uint64_t rng_seed, int64_t problem_offset) {
     pik::RestartArgs r = {};
@@ -1688,6 +1729,7 @@ int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int
     HIP_TRY(hipSetDevice(s->device));
     pik::SearchArgs a;
     if (int rc = search_args(s, p, slot, B, max_attempts, d, rng_seed, problem_offset, a)) return rc;
+    if (int rc = search_gate(s, pk, slot, (hipStream_t)stream, a)) return rc;
     return ops->solve(s, pk, a, (hipStream_t)stream, slot);
 }
 
@@ -1708,6 +1750,7 @@ int32_t pikamd_search_batch(pikamd_solver* s, const pikamd_params* p, int64_t B,
     if (int rc = stage_search(st, s, h, B, max_attempts, d)) return rc;
     pik::SearchArgs a;
     if (int rc = search_args(s, p, Staging::SLOT, B, max_attempts, d, rng_seed, problem_offset, a)) return rc;
+    if (int rc = search_gate(s, pk, Staging::SLOT, st.stream(), a)) return rc;
     if (int rc = st.upload()) return rc;
     return st.finish(ops->solve(s, pk, a, st.stream(), Staging::SLOT));
 }
@@ -1743,14 +1786,17 @@ int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::Param
     char* w = (char*)buf.p;
     unsigned* n_list = (unsigned*)(s->counters + pik::COUNTER_BLOCK * (size_t)slot + 128);
     r.guess = (double*)(w + off_guess);
-    r.row_solution = (const double*)(w + off_sol);
+    r.row_solution = (double*)(w + off_sol);
     r.row_cost = (const double*)(w + off_cost);
     r.row_stats = w + off_stats;
-    r.row_status = (const int*)(w + off_status);
+    r.row_status = (int*)(w + off_status);
     r.open = (int*)(w + off_open);
     r.list = (int*)(w + off_list);
     r.n_list = n_list;
     r.every = (r.all_solution || r.all_status) ? 1 : 0;
+    r.goal = d_goal;
+    r.seed = d_seed;
+    if (int rc = gate_for_call(s, pk, slot, stream, &r.gate, &r.gate_joint, &r.gate_params)) return rc;
     pik::BatchRecord rec;
     std::memset(&rec, 0, sizeof rec);
     rec.B = r.B;
@@ -1784,6 +1830,8 @@ int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::Param
         }
         r.attempt = a;
         r.last = (a == r.K - 1) ? 1 : 0;
+        if (r.gate)
+            if (int rc = ops->gate(s, pk, r, stream, slot)) return give_up(rc);
         if (int rc = ops->fold(s, pk, r, stream, slot)) return give_up(rc);
         if (sync_between && !r.last) {
             unsigned cnt = 0;
@@ -1840,6 +1888,46 @@ int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int
     if (int rc = st.upload()) return rc;
     return st.finish(run_search_global(s, p, pk, ops, restart_args(B, max_attempts, d, rng_seed, problem_offset), d.goal,
                                        d.seed, st.stream(), Staging::SLOT, true));
+}
+
+} // extern "C"
+
+extern "C" {
+
+// ---- the approximate-solution gate (src/pick_ik_plugin.cpp:219-267) --------------------------------
+
+int32_t pikamd_set_approximate_gate(pikamd_solver* s, const pikamd_gate* gate) {
+    if (int rc = check_solver(s)) return rc;
+    SolverExt* x = ext_of(s);
+    x->gate_set = gate != nullptr;
+    if (gate) x->gate = *gate;
+    return 0;
+}
+
+// the definition of the header, literally: pikamd_cost_batch under p', then the joint test
+int32_t pikamd_gate_batch(pikamd_solver* s, const pikamd_params* p, const pikamd_gate* gate, int64_t n,
+                          const double* goal_pos_quat, const double* seed, const double* q, int32_t* pass) {
+    if (int rc = check_solver(s)) return rc;
+    if (!p) return fail(PIKAMD_EINVAL, "params is NULL");
+    if (!gate || !goal_pos_quat || !seed || !q || !pass)
+        return fail(PIKAMD_EINVAL, "pikamd_gate_batch: gate, goal_pos_quat, seed, q and pass must not be NULL");
+    if (n < 0) return fail(PIKAMD_EINVAL, "pikamd_gate_batch: n = %lld: expected n >= 0", (long long)n);
+    if (s->opt.soa) return fail(PIKAMD_EINVAL, "joint_layout soa: not with pikamd_gate_batch (its arrays are [n][dof])");
+    if (n == 0) return 0;
+    pikamd_params pg = *p;
+    if (gate->cost_threshold > 0.0) {
+        pg.cost_threshold = gate->cost_threshold;
+    } else {
+        pg.center_joints_weight = pg.avoid_joint_limits_weight = pg.minimal_displacement_weight = 0.0;
+    }
+    if (int rc = pikamd_cost_batch(s, &pg, n, goal_pos_quat, seed, q, nullptr, pass)) return rc;
+    if (gate->joint_threshold > 0.0) {
+        const size_t d = (size_t)s->chain.dof;
+        for (size_t i = 0; i < (size_t)n; ++i)
+            for (size_t j = 0; j < d; ++j)
+                if (std::fabs(q[i * d + j] - seed[i * d + j]) > gate->joint_threshold) pass[i] = 0;
+    }
+    return 0;
 }
 
 } // extern "C"

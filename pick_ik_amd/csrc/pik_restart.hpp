@@ -1,5 +1,5 @@
 // pik_restart.hpp -- memetic IK with random restarts (pikamd_search_global_batch): the launcher of a restart attempt
-// and the two small kernels that run between the attempts.
+// and the small kernels that run between the attempts.
 //
 // searchPositionIK (src/pick_ik_plugin.cpp:145-291) solves, and when no solution came back draws a random valid
 // configuration and solves again from there.  Attempt 0 of a call is the existing launch of pikamd_solve_batches
@@ -54,6 +54,40 @@ __global__ __launch_bounds__(WAVE) void restart_prepare_kernel(const ConstsK<D>*
 #pragma unroll
     for (int j = 0; j < D; ++j) r.guess[b * D + j] = valid ? q[j] : drawn[j];
     r.open[b] = 1;
+}
+
+// The approximate-solution gate (src/pick_ik_plugin.cpp:219-267), between attempt r.attempt and its fold when the call
+// is gated, one thread per problem: a row the attempt wrote with status > 0 is evaluated under p' (r.gate_params: the
+// flavour's own evaluate, the routine cost_kernel calls) and held to the joint threshold; a refused row becomes
+// PIKAMD_GATE_REFUSED and the seed, its cost and counters stay, and the fold -- which is what it was -- reads the gated
+// row.  A kernel of its own: the fold runs in every call, gated or not, without a stack, and the exact flavours'
+// evaluation of a long chain is a call.
+template <int D, bool MULTI = false>
+__global__ __launch_bounds__(WAVE) void restart_gate_kernel(const ConstsK<D>* __restrict__ kc, RestartArgs r) {
+    PIK_CONSTS(kc);
+    const long long b = (long long)blockIdx.x * WAVE + threadIdx.x;
+    if (b >= r.B) return;
+    const bool ran = r.every != 0 || r.open[b] != 0;
+    if (!ran || !(r.row_status[b] > 0)) return;
+    typename GoalSel<MULTI>::type g;
+    load_goals<D>(c, r.goal, b, g);
+    double q[D], sd[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        q[j] = r.row_solution[b * D + j];
+        sd[j] = r.seed[b * D + j];
+    }
+    EvalOut e;
+    evaluate<D>(c, *(const PIK_CONSTANT ParamsK*)r.gate_params, g, sd, q, e);
+    bool pass = e.sol;
+    if (r.gate_joint > 0.0) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) pass = pass && !(fabs(q[j] - sd[j]) > r.gate_joint);
+    }
+    if (pass) return;
+    r.row_status[b] = PIKAMD_GATE_REFUSED_K;
+#pragma unroll
+    for (int j = 0; j < D; ++j) r.row_solution[b * D + j] = sd[j];
 }
 
 // Behind attempt r.attempt, one thread per problem, one wavefront per block.
@@ -131,6 +165,18 @@ int launch_restart_fold(pikamd_solver* s, const ParamsK& pk, const RestartArgs& 
     const ConstsK<D>* kc = nullptr;
     if (int rc = upload_consts<D>(s, &pk, slot, st, &kc)) return rc;
     hipLaunchKernelGGL(restart_fold_kernel<D>, dim3((unsigned)((r.B + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, kc, r);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <int D>
+int launch_restart_gate(pikamd_solver* s, const ParamsK& pk, const RestartArgs& r, hipStream_t st, int slot) {
+    if (r.B == 0 || !r.gate) return 0;
+    const ConstsK<D>* kc = nullptr;
+    if (int rc = upload_consts<D>(s, &pk, slot, st, &kc)) return rc;
+    const dim3 g((unsigned)((r.B + WAVE - 1) / WAVE)), b(WAVE);
+    if (s->n_tips > 1) hipLaunchKernelGGL((restart_gate_kernel<D, true>), g, b, 0, st, kc, r);
+    else hipLaunchKernelGGL(restart_gate_kernel<D>, g, b, 0, st, kc, r);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -367,7 +413,7 @@ int launch_restart_attempt(pikamd_solver* s, const pikamd_params* p, const Param
 template <int D>
 const RestartOps* make_restart_ops() {
     static const RestartOps ops = {&restart_reserve<D>, &launch_restart_prepare<D>, &launch_restart_fold<D>,
-                                   &launch_restart_attempt<D>};
+                                   &launch_restart_gate<D>, &launch_restart_attempt<D>};
     return &ops;
 }
 

@@ -20,8 +20,8 @@ struct RestartArgs {
     double* guess;                // [B][D] scratch: init[b]
     unsigned long long rng_seed;  // the CALLER's seed: the key of the restart draws
     long long problem_offset;
-    const double* row_solution;   // [B][D] the finished attempt's outputs
-    const int* row_status;        // [B]
+    double* row_solution;         // [B][D] the finished attempt's outputs (restart_gate_kernel rewrites a refused row)
+    int* row_status;              // [B]
     const double* row_cost;       // [B]
     const void* row_stats;        // [B] StatsK
     double* solution;             // [B][D] primary outputs
@@ -34,6 +34,12 @@ struct RestartArgs {
     int* open;                    // [B] scratch: 1 while the loop has not closed the problem
     int* list;                    // [B] scratch: the problems of the next attempt
     unsigned* n_list;             // their number (the slot's n_list[0]: zero when the fold starts)
+    // the approximate-solution gate (restart_gate_kernel, in front of the fold): SearchArgs has the same three fields
+    const double* goal;           // [B][n_tips][7]
+    const double* seed;           // [B][D]
+    int gate;                     // 0: no gate, the gate kernel is not launched
+    double gate_joint;
+    const ParamsK* gate_params;
 };
 
 struct RestartOps {
@@ -42,6 +48,8 @@ struct RestartOps {
     int (*reserve)(pikamd_solver*, const pikamd_params*, const ParamsK&, long long B, int slot);
     int (*prepare)(pikamd_solver*, const ParamsK&, const RestartArgs&, hipStream_t, int slot);
     int (*fold)(pikamd_solver*, const ParamsK&, const RestartArgs&, hipStream_t, int slot);
+    // between an attempt and its fold when the call is gated (r.gate): the attempt's rows through the gate
+    int (*gate)(pikamd_solver*, const ParamsK&, const RestartArgs&, hipStream_t, int slot);
     // one attempt a >= 1: the pass loop over the problems of `list` (device memory, their number in the slot's
     // n_list[0]); `rec`: ONE record of B problems (host copy, device pointers); n_hint: the number of listed
     // problems where the host knows it (sizes grids, changes no result), else < 0

@@ -34,6 +34,7 @@
 namespace pik {
 
 constexpr uint32_t STREAM_RESTART = 3u; // (streams 1 and 2: pik_math.hpp)
+constexpr int PIKAMD_GATE_REFUSED_K = -1002; // PIKAMD_GATE_REFUSED
 
 // (hi - lo) * u + lo with every operation rounded on its own, whatever contraction the flavour is compiled with
 // (the fast flavour's uniform_real is one fused expression): the restart states are the same doubles in all flavours
@@ -117,8 +118,10 @@ __device__ __forceinline__ void search_state(CK<D> c, const SearchArgs& a, long 
 }
 
 // Behind the descent of attempt `att` of problem b: the post-loop of ik_gradient (src/ik_gradient.cpp:130-138) as
-// ik_gradient_kernel has it, the attempt's row (stored by the lanes with `store`: the unit's first lane), in the
-// sequential schedule the primary outputs while the problem is open.
+// ik_gradient_kernel has it, the approximate-solution gate where the handle has one (a refused answer is
+// PIKAMD_GATE_REFUSED and the seed; everything below -- the row, the primary outputs, whether the problem stays open,
+// and with the row search_finalize_kernel's winner -- uses the gated status), the attempt's row (stored by the lanes
+// with `store`: the unit's first lane), in the sequential schedule the primary outputs while the problem is open.
 // `run`: the unit ran this attempt (it is open, or every attempt is wanted).  All lanes of the wavefront call this
 // together.
 template <int D, typename G>
@@ -133,13 +136,32 @@ __device__ __forceinline__ void search_attempt(CK<D> c, PK p, const SearchArgs& 
     } else if (p.approx) {
         status = 2;
     }
-    double first_cost = 0.0; // cost of the attempt's start, reported on failure
-    if (__any(run && status < 0)) {
+    // One evaluation per attempt at the most, with operands chosen by what the call needs: the cost of the attempt's
+    // start, reported on failure, or -- a.gate -- the approximate-solution gate on the attempt's answer
+    // (src/pick_ik_plugin.cpp:219-267) under the parameters p' of pikamd_gate_batch.  The host sets a.gate only with
+    // return_approximate_solution, and then every status is > 0: a call needs the one or the other, never both.
+    const bool solved = status > 0;
+    double first_cost = 0.0;
+    if (__any(run && (a.gate != 0 || !solved))) {
         double cur[D];
-        search_start<D>(c, a, b, att, cur);
+        if (a.gate == 0) {
+            search_start<D>(c, a, b, att, cur);
+        } else {
+#pragma unroll
+            for (int j = 0; j < D; ++j) cur[j] = s.best[j];
+        }
+        const PIK_CONSTANT ParamsK* pe = a.gate != 0 ? (const PIK_CONSTANT ParamsK*)a.gate_params : &p;
         EvalOut e;
-        evaluate<D>(c, p, g, sd, cur, e);
+        evaluate<D>(c, *pe, g, sd, cur, e);
         first_cost = e.cost;
+        if (a.gate != 0 && solved) {
+            bool pass = e.sol;
+            if (a.gate_joint > 0.0) {
+#pragma unroll
+                for (int j = 0; j < D; ++j) pass = pass && !(fabs(s.best[j] - sd[j]) > a.gate_joint);
+            }
+            status = pass ? status : PIKAMD_GATE_REFUSED_K;
+        }
     }
     StatsK st;
     st.cost_evals = (s.found == 2) ? 0 : 1 + (long long)s.steps * (2 * D + 3);
@@ -147,7 +169,7 @@ __device__ __forceinline__ void search_attempt(CK<D> c, PK p, const SearchArgs& 
     st.wipeouts = 0;
     st.pool_erasures = 0;
     st.reserved = 0;
-    const double cost = (status > 0) ? s.best_cost : first_cost;
+    const double cost = solved ? s.best_cost : first_cost; // (a refused answer keeps the cost the solve returned)
     if (run && store) {
         const long long row = b * a.K + att;
         if (a.row_solution) {

@@ -33,7 +33,28 @@ struct SearchArgs {
     int* row_status;              // [B][K] or null
     double* row_cost;             // [B][K], parallel schedule only
     void* row_stats;              // [B][K] StatsK, parallel schedule only
+    // The approximate-solution gate of the handle (pikamd_set_approximate_gate), applied behind every attempt.  The
+    // host sets `gate` only for a call with return_approximate_solution.  gate_params: the parameters p' of
+    // pikamd_gate_batch in device memory -- the evaluation reads its parameters through the constant address space,
+    // where a kernel cannot make a copy; they are not in ConstsK, which every other kernel reads.
+    int gate;                     // 0: no gate (the fields below are not read)
+    double gate_joint;            // approximate_solution_joint_threshold (not > 0: no limit)
+    const ParamsK* gate_params;
 };
+
+// p' of pikamd_gate_batch, from the call's converted parameters: the gate's cost threshold in place of the call's when
+// it is > 0, else no joint goal (src/pick_ik_plugin.cpp:240-242: no goal is tested; the frame tests stay)
+inline ParamsK gate_params_k(const ParamsK& pk, double cost_threshold) {
+#pragma clang fp contract(off)
+    ParamsK g = pk;
+    if (cost_threshold > 0.0) {
+        g.cost_thr_sq = cost_threshold * cost_threshold;
+    } else {
+        g.goal_mask = 0;
+        g.w_center_sq = g.w_limits_sq = g.w_disp_sq = 0.0;
+    }
+    return g;
+}
 
 struct SearchOps {
     int (*solve)(pikamd_solver*, const ParamsK&, const SearchArgs&, hipStream_t, int slot);

@@ -535,6 +535,38 @@ class Solver {
         return r;
     }
 
+    // The approximate-solution gate (src/pick_ik_plugin.cpp:219-267; pikamd_gate_batch): is `q` acceptable as an
+    // approximate solution -- the solution test of `costs` under approximate_solution_cost_threshold (<= 0: no goal
+    // is tested, the frame tests stay), then no variable further than approximate_solution_joint_threshold from
+    // `seed` (not > 0: no limit).  goals: one pose per tip.
+    bool gate(const std::vector<double>& q, const std::vector<Pose>& goals, const std::vector<double>& seed,
+              const CostSpec& costs, double cost_threshold, double joint_threshold) const {
+        check_size(q);
+        check_size(seed);
+        if (static_cast<int>(goals.size()) != n_tips_) throw std::invalid_argument("pick_ik_amd: one goal per tip is required");
+        const pikamd_params p = to_params(costs, nullptr, nullptr, true);
+        const pikamd_gate g = {cost_threshold, joint_threshold};
+        std::vector<double> g7;
+        for (const Pose& pose : goals) {
+            const double v[7] = {pose.x, pose.y, pose.z, pose.qw, pose.qx, pose.qy, pose.qz};
+            g7.insert(g7.end(), v, v + 7);
+        }
+        int32_t pass = 0;
+        if (pikamd_gate_batch(h_, &p, &g, 1, g7.data(), seed.data(), q.data(), &pass) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return pass != 0;
+    }
+    // pikamd_set_approximate_gate: the gate the two *_search_batch calls above apply behind every attempt when
+    // approx_solution is set -- a refused answer is PIKAMD_GATE_REFUSED and the seed, and the search restarts;
+    // clear_approximate_gate: none (the default)
+    void set_approximate_gate(double cost_threshold, double joint_threshold) const {
+        const pikamd_gate g = {cost_threshold, joint_threshold};
+        if (pikamd_set_approximate_gate(h_, &g) != 0) throw std::runtime_error(pikamd_last_error());
+    }
+    void clear_approximate_gate() const {
+        if (pikamd_set_approximate_gate(h_, nullptr) != 0) throw std::runtime_error(pikamd_last_error());
+    }
+
     pikamd_solver* handle() const { return h_; }
 
     // pikamd_self_test: every kernel variant against the one-lane kernel on n generated targets of this

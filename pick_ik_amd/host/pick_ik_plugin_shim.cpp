@@ -624,27 +624,16 @@ class PickIKPlugin : public kinematics::KinematicsBase {
                 // REGULAR frame tests (the approximate pose thresholds are computed there but the
                 // test is made from `frame_tests`) and from the goals under
                 // approximate_solution_cost_threshold (no goals when that is <= 0), then the
-                // joint-jump limit
-                pick_ik_amd::CostSpec gate = costs;
+                // joint-jump limit.  The library states that gate once (Solver::gate, pikamd_gate_batch: the one the
+                // batched searches apply on the device); the goals of the host callback are tested here
                 double const act = P("approximate_solution_cost_threshold", 0.0);
-                if (act <= 0.0) {
-                    gate.center_joints_weight = gate.avoid_joint_limits_weight = gate.minimal_displacement_weight = 0.0;
-                } else {
-                    gate.cost_threshold = act;
-                }
-                bool valid = solver_->evaluate(solution, g, ik_seed_state, gate).is_solution;
+                double const jt = P("approximate_solution_joint_threshold", 0.0);
+                bool valid = solver_->gate(solution, g, ik_seed_state, costs, act, jt);
                 if (valid && cost_function && act > 0.0) { // the callback's goals are goals too
                     double worst = 0.0;
                     callback_cost(solution, worst);
                     valid = worst < act * act;
                 }
-                double const jt = P("approximate_solution_joint_threshold", 0.0);
-                if (valid && jt > 0.0)
-                    for (size_t i = 0; i < solution.size(); ++i)
-                        if (std::abs(solution[i] - ik_seed_state[i]) > jt) {
-                            valid = false;
-                            break;
-                        }
                 if (!valid) {
                     error_code.val = error_code.NO_IK_SOLUTION;
                     solution = ik_seed_state;

@@ -98,6 +98,15 @@ class _MultiChain(C.Structure):
     ]
 
 
+class Gate(C.Structure):
+    """pikamd_gate: the approximate-solution gate (src/pick_ik_plugin.cpp:219-267)"""
+    _fields_ = [("cost_threshold", C.c_double), ("joint_threshold", C.c_double)]
+
+
+#: status of an answer the gate refused (PIKAMD_GATE_REFUSED)
+GATE_REFUSED = -1002
+
+
 class Batch(C.Structure):
     """pikamd_batch: one batch of a multi-batch call (device or host pointers, see the header)."""
 
@@ -168,6 +177,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_solve_paths", "pikamd_solve_paths_device", "pikamd_path_kernel_name",
     "pikamd_search_batch", "pikamd_search_batch_device", "pikamd_search_kernel_name",
     "pikamd_debug_regime", "pikamd_search_global_batch", "pikamd_search_global_batch_device",
+    "pikamd_gate_batch", "pikamd_set_approximate_gate",
 )
 
 _libs = {}
@@ -269,6 +279,10 @@ def lib(strict: bool = False):
     L.pikamd_search_global_batch_device.restype = C.c_int32
     L.pikamd_search_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, ip]
     L.pikamd_search_kernel_name.restype = C.c_char_p
+    L.pikamd_gate_batch.argtypes = [vp, C.POINTER(Params), C.POINTER(Gate), C.c_int64, dp, dp, dp, ip]
+    L.pikamd_gate_batch.restype = C.c_int32
+    L.pikamd_set_approximate_gate.argtypes = [vp, C.POINTER(Gate)]
+    L.pikamd_set_approximate_gate.restype = C.c_int32
     up = C.POINTER(C.c_uint32)
     L.pikamd_debug_regime.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, ip, up, up, ip]
     L.pikamd_debug_regime.restype = C.c_int32
@@ -515,6 +529,28 @@ class Solver:
         self._chk(self._L.pikamd_cost_batch(self._h, C.byref(params), n, _dp(goal), _dp(seed), _dp(q),
                                        _dp(cost), _ip(sol)))
         return cost, sol
+
+    def gate(self, params: Params, gate: Gate, goal_pos_quat, seed, q) -> np.ndarray:
+        """pikamd_gate_batch: pass [n] (bool) of n (goal, seed, q) triples (goal / seed broadcast if 1-D) -- the
+        reference's approx_solution_valid: the solution test under the gate's cost threshold, then the joint limit."""
+        q = _f64(q).reshape(-1, self.dof)
+        n = q.shape[0]
+        g7 = 7 * self.n_tips
+        goal = np.ascontiguousarray(np.broadcast_to(_f64(goal_pos_quat).reshape(-1, g7), (n, g7)))
+        seed = np.ascontiguousarray(np.broadcast_to(_f64(seed).reshape(-1, self.dof), (n, self.dof)))
+        ok = np.zeros(n, dtype=np.int32)
+        self._chk(self._L.pikamd_gate_batch(self._h, C.byref(params), C.byref(gate), n, _dp(goal), _dp(seed), _dp(q),
+                                            _ip(ok)))
+        return ok != 0
+
+    def set_approximate_gate(self, cost_threshold: float = 0.0, joint_threshold: float = 0.0) -> None:
+        """The gate search_batch / search_global_batch apply behind every attempt of a call with
+        return_approximate_solution: a refused answer is GATE_REFUSED and the search restarts."""
+        self._chk(self._L.pikamd_set_approximate_gate(self._h, C.byref(Gate(cost_threshold, joint_threshold))))
+
+    def clear_approximate_gate(self) -> None:
+        """no gate (the default): every result is what it was"""
+        self._chk(self._L.pikamd_set_approximate_gate(self._h, None))
 
     def gd_step(self, params: Params, goal_pos_quat, seed, local, best, local_cost, best_cost):
         """One step() of src/ik_gradient.cpp:24-94 on n GradientIk states."""
