@@ -279,12 +279,19 @@ def _host_api_lines():
     return out
 
 
+#: the host-only launcher headers pik_inst.hip reads: they enqueue kernels and define none (no __global__, __device__,
+#: __constant__ or __shared__ in them: tests/test_build_cpu.py), so flavour_sha leaves their lines out
+HOST_LAUNCH_HEADERS = ("pik_launch.hpp", "pik_memetic_plan.hpp")
+
+
 def flavour_sha(namespace: str, dof: int = 7) -> str:
     """Hash of the DEVICE source of one kernel flavour: pik_inst.hip preprocessed with the flavour's flags
     (`hipcc -E`, device side), reduced to the lines that come from this repository's own files (csrc/, include/).
     Comments and the branches the flavour's macros switch off are not in it, so an edit of pik_exact.hpp or of a
     PIK_STRICT block leaves the hash of the fast flavours alone; neither are the header's host-only declarations
-    (_host_api_lines).  The flags are part of the hash.  bench.py compares it
+    (_host_api_lines) nor the host-only launcher headers (HOST_LAUNCH_HEADERS), so a change of how the kernels are
+    enqueued leaves every hash alone.  Every other file -- pik_solver.hpp and pik_host.hpp included -- is hashed, host
+    functions and all.  The flags are part of the hash.  bench.py compares it
     with the hash stored beside the PMC counters of a flavour (profiles/roofline_inputs.json: roofline.inputs_stale)."""
     key = (namespace, dof)
     if key in _flavour_sha_cache:
@@ -303,7 +310,7 @@ def flavour_sha(namespace: str, dof: int = 7) -> str:
         if line.startswith("# ") and '"' in line:  # line marker: # <n> "<file>" <flags>
             f = line.split('"')[1]
             rp = os.path.realpath(f if os.path.isabs(f) else os.path.join(CSRC, f))
-            keep = rp.startswith(own[0]) or rp == own[1]
+            keep = (rp.startswith(own[0]) and os.path.basename(rp) not in HOST_LAUNCH_HEADERS) or rp == own[1]
             in_header = rp == own[1]
             lineno = int(line.split()[1])  # (the line the NEXT output line comes from)
             continue

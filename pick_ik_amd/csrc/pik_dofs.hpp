@@ -1,8 +1,8 @@
 // pik_dofs.hpp -- the chain lengths the library is built for, written out ONCE, and what is generated from the list:
 // the per-length ops functions a kernel family's translation units export (declarations, lookup, definition) and the
 // memetic kernel variants the routed and the restart launcher name.  Host-side macros only, no device code; not read
-// by pik_inst.hip (whose launch_ops_d<N> / launch_ops() in pik_solver.hpp stay written out by hand: their text is
-// part of the hash the committed kernel profiles are keyed by).
+// by pik_inst.hip (whose launch_ops_d<N> / launch_ops() in pik_solver.hpp stay written out by hand: pik_solver.hpp is
+// part of the text pick_ik_amd/build.py flavour_sha hashes, and the pinned hashes say that text is untouched).
 #pragma once
 
 // X(N, ...) for N = 1..16
@@ -38,9 +38,10 @@
 
 // The memetic kernel variants (lanes per elite, several tip frames?, wavefronts per SIMD) a launcher outside
 // pik_inst.hip names.  They are NOT compiled there: each is declared as an explicit instantiation that lives in the
-// flavour's pik_inst object of this length.  The routed launcher names the forms for one tip frame, the restart
-// launcher all of them.  The two-per-SIMD build exists up to nine joints; the 16 / 8-lane forms for several tips
-// are the product flavours' cooperative descent.
+// flavour's pik_inst object of this length.  Both launchers go through the shared switch from a variant id to its
+// kernel (pik_launch.hpp with_variant_kernel), which names all of them -- the routed launcher enqueues the forms for
+// one tip frame only.  The two-per-SIMD build exists up to nine joints; the 16 / 8-lane forms for several tips are
+// the product flavours' cooperative descent.
 #if PIK_INST_D <= 9
 #define PIK_MEMETIC_TWO_PER_SIMD(X) X(1, false, 2)
 #else

@@ -6,18 +6,13 @@
 
 #include "pik_kernels.hpp"
 #include "pik_solver.hpp"
+#include "pik_memetic_plan.hpp"
 
 namespace pik {
 
 static_assert(sizeof(StatsK) == sizeof(pikamd_stats), "stats layout");
 static_assert(sizeof(BatchRecord) == sizeof(BatchK), "batch record layout");
 static_assert(offsetof(BatchRecord, completed) == offsetof(BatchK, completed), "batch record layout");
-
-inline int pow2ceil_log2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
 
 // Makes the slot's device constants buffer hold this call's chain + params.  The upload is
 // skipped when the slot already holds the same bytes (the common case: same robot, same params
@@ -148,63 +143,146 @@ inline int upload_batch_table(pikamd_solver* s, BatchRecord* batches, int n, hip
     return 0;
 }
 
-// launch schedule of a memetic call
-struct Schedule {
-    // forced lanes per elite (experiments / tests): passes starting at generation >= lpe_from[i] run
-    // with lpe_of[i]; n_sched == 0: adaptive (the default, see launch_solve)
-    int lpe_from[4] = {0, 0, 0, 0}, lpe_of[4] = {1, 1, 1, 1}, n_sched = 0;
-    int marks[16], n_marks = 0;
-    bool occ2_ok = true;
-    long long occ2_from = 0;
-};
+// ---- a memetic call: what its three launchers -- launch_solve below, the routed launcher (pik_route.hpp), the
+// launcher of a restart attempt (pik_restart.hpp) -- share besides the plan (pik_memetic_plan.hpp) ----
+static_assert(WAVE == PLAN_WAVE, "the plan's wavefront");
 
-// the handle's scheduling options (pikamd_set_option) -> the launch schedule of one call
-inline void make_schedule(const pikamd_solver* s, const ParamsK& pk, int gs, int S, Schedule& sc) {
-    const bool multi = s->n_tips > 1;
-    const SolverOptions& o = s->opt;
-    auto ok = [&](int v) { return lpe_allowed(s, v, gs, S, multi); };
-    if (o.lpe > 0 && ok(o.lpe)) {
-        sc.lpe_of[0] = o.lpe;
-        sc.n_sched = 1;
-    }
-    if (o.n_sched > 0) {
-        bool good = true;
-        for (int i = 0; i < o.n_sched; ++i) good = good && ok(o.sched_of[i]);
-        if (good) {
-            sc.n_sched = o.n_sched;
-            for (int i = 0; i < o.n_sched; ++i) {
-                sc.lpe_from[i] = o.sched_from[i];
-                sc.lpe_of[i] = o.sched_of[i];
-            }
-        }
-    }
-    if (S != 1 && sc.n_sched > 1) sc.n_sched = 1; // (species: one choice for all passes when forced)
-    if (multi && sc.n_sched > 0 && !ok(sc.lpe_of[0])) sc.n_sched = 0; // (a request several tips cannot serve: adaptive)
-    if (multi && sc.n_sched > 1) sc.n_sched = 1;
-    (void)ok;
-    // Compaction passes: generation marks at which still-running problems are parked in HBM and
-    // re-packed densely for the next launch (results do not depend on the marks).  Dense in the
-    // tail: the survivor count halves every ~10 generations, and every pass re-chooses the lanes
-    // per elite for the survivors it gets.
-    {
-        static const int default_marks[] = {2, 4, 8, 12, 16, 24, 32, 40, 48, 64, 80};
-        const int* m = o.passes_set ? o.marks : default_marks;
-        const int n = o.passes_set ? o.n_marks : (int)(sizeof default_marks / sizeof default_marks[0]);
-        (void)S; // (several species park and resume like one: a record per (problem, species))
-        for (int i = 0; i < n && sc.n_marks < 15; ++i)
-            if (m[i] > 0 && m[i] < pk.max_generations && (sc.n_marks == 0 || m[i] > sc.marks[sc.n_marks - 1]))
-                sc.marks[sc.n_marks++] = m[i];
-    }
-    sc.occ2_ok = S == 1;
-    // first-pass wavefronts from which the two-per-SIMD variant pays (measured crossover with
-    // overlapped batches on 1024 SIMDs: slower at 512, +3 % at 640, +5 % at 768, +26 % at 1024)
-    sc.occ2_from = (long long)s->num_cu * 4 * 5 / 8;
-    if (o.two_per_simd >= 0) {
-        sc.occ2_ok = sc.occ2_ok && o.two_per_simd != 0;
-        if (o.two_per_simd > 1) sc.occ2_from = o.two_per_simd; // (explicit threshold)
-    }
-    if (o.force_occ2) sc.occ2_from = 0;
+// the plan's regime input: are three or more OTHER calls of this handle still in flight?
+inline bool others_busy(pikamd_solver* s, int slot) {
+    int others = 0;
+    for (int k = 0; k < N_DEVICE_SLOTS + N_HOST_JOBS; ++k)
+        if (k != slot && s->slot_event_used[k] && hipEventQuery(s->slot_event[k]) == hipErrorNotReady) ++others;
+    (void)hipGetLastError(); // (hipErrorNotReady is an answer, not a failure)
+    return others >= 3;
 }
+
+// f(the memetic kernel with this variant id)
+template <int D, class F>
+int with_variant_kernel(int id, F f) {
+    switch (id) {
+        case 5: return f(memetic_kernel<D, 16>);
+        case 4: return f(memetic_kernel<D, 8>);
+        case 3: return f(memetic_kernel<D, 4>);
+        case 2: return f(memetic_kernel<D, 2>);
+        case 7:
+            if constexpr (D <= 9) return f(memetic_kernel<D, 1, false, 2>);
+            return 0;
+#if !defined(PIK_STRICT)
+        case 10: return f(memetic_kernel<D, 16, true>);
+        case 9: return f(memetic_kernel<D, 8, true>);
+#endif
+        case 8: return f(memetic_kernel<D, 2, true>);
+        case 6: return f(memetic_kernel<D, 1, true>);
+        default: return f(memetic_kernel<D, 1>);
+    }
+}
+
+// waves per CU of each kernel variant: asked once per handle and FLAVOUR (the general and the exact kernels are
+// different code with different register counts: a handle switched between them by the option "arithmetic"
+// must not size one flavour's grids by the other's figure)
+#define PIK_OCC_ROW (PIK_COMMON ? (PIK_NO_GOALS ? 1 : 2) : (PIK_XF ? 3 : 0))
+
+// the slot's scratch for a memetic call of B problems, S species (the plan's layout with this length's record rows)
+template <int D>
+MemeticScratch memetic_scratch(const pikamd_solver* s, const ParamsK& pk, long long B, int S) {
+    return MemeticScratch(B, S, pk.population, D, chain_has_unbounded(s), (size_t)StateRows<D>::D_ROWS(pk.elites),
+                          StateRows<D>::L_ROWS, StateRows<D>::I_ROWS);
+}
+
+template <int D>
+struct MemeticCall {
+    pikamd_solver* s;
+    hipStream_t st;
+    int slot;
+    const ConstsK<D>* kc = nullptr;
+    SolveArgs a; // the caller's (batches, seed, B) + what the plan and the pass fill in
+    MemeticPlan pl;
+    int* lists[2] = {nullptr, nullptr};
+    unsigned char* cblk = nullptr; // the slot's counter block: u64 work[16] | u32 n_list[17] @128 | u32 done[16] @256
+    unsigned long long* c_work = nullptr;
+    unsigned* c_nlist = nullptr;
+    unsigned* c_done = nullptr;
+
+    MemeticCall(pikamd_solver* s_, const pikamd_params* p, const ParamsK& pk, hipStream_t st_, int slot_, const SolveArgs& a0)
+        : s(s_), st(st_), slot(slot_), a(a0) {
+        plan_begin(s, p, pk, pl);
+        a.gs_log2 = pl.gs_log2;
+        a.species = pl.S;
+        a.sp_log2 = pl.sp_log2;
+    }
+    MemeticScratch scratch(const ParamsK& pk, long long B) const { return memetic_scratch<D>(s, pk, B, pl.S); }
+    // the slot's scratch (parked state and survivor lists only for a call with passes) and its counter block
+    void bind(const MemeticScratch& lay, bool passes) {
+        char* base = (char*)s->slot_state[slot].p;
+        a.pop = lay.has_unbounded ? (double*)(base + lay.off_pop) : nullptr;
+        a.pop_stride = (long long)lay.pop_stride;
+        a.cap = a.B;
+        a.st_d = passes ? (double*)(base + lay.off_d) : nullptr;
+        a.st_l = passes ? (long long*)(base + lay.off_l) : nullptr;
+        a.st_i = passes ? (int*)(base + lay.off_i) : nullptr;
+        lists[0] = passes ? (int*)(base + lay.off_list) : nullptr;
+        lists[1] = passes ? lists[0] + a.cap : nullptr;
+        cblk = s->counters + COUNTER_BLOCK * (size_t)slot;
+        c_work = (unsigned long long*)cblk;
+        c_nlist = (unsigned*)(cblk + 128);
+        c_done = (unsigned*)(cblk + 256);
+    }
+    // wavefronts the chip holds of every candidate
+    int capacities() {
+        for (int i = 0; i < pl.n_var; ++i) {
+            int& per_cu = s->occupancy_cache[PIK_OCC_ROW][pl.var[i].id];
+            if (per_cu == 0) {
+                int asked = 0;
+                if (int rc = with_variant_kernel<D>(pl.var[i].id, [&](auto kernel) -> int {
+                        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&asked, kernel, WAVE, 0));
+                        return 0;
+                    }))
+                    return rc;
+                per_cu = asked < 1 ? 1 : asked;
+            }
+            pl.var[i].capacity = (long long)s->num_cu * per_cu;
+        }
+        return 0;
+    }
+    // pass k of n_marks + 1: from the survivors of pass k - 1 (pass 0: every problem) to the list of its own
+    void pass(int k, const int* marks, int n_marks) {
+        a.fresh = (k == 0);
+        a.pause_gen = (k < n_marks) ? marks[k] : 0x7fffffff;
+        a.list_in = (k == 0) ? nullptr : lists[(k - 1) & 1];
+        a.n_in = (k == 0) ? nullptr : c_nlist + k;
+        a.list_out = n_marks ? lists[k & 1] : nullptr;
+        a.n_out = n_marks ? c_nlist + (k + 1) : nullptr;
+        a.work_counter = c_work + k;
+        a.done = c_done + k;
+    }
+    // candidate v for survivor counts in (lo, hi], its grid sized for n problems
+    int launch(int v, long long n, unsigned lo, unsigned hi) {
+        a.sel_lo = lo;
+        a.sel_hi = hi;
+        const dim3 g((unsigned)plan_grid(n, pl.groups_per_wave(v), pl.var[v].capacity)), b(WAVE);
+        return with_variant_kernel<D>(pl.var[v].id, [&](auto kernel) -> int {
+            hipLaunchKernelGGL(kernel, g, b, 0, st, kc, a);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+    }
+    // what the host's rule enqueues for the pass (plan_pass)
+    int launch_pass(const RangeTable& t, int start_gen, long long size, long long known, bool counted) {
+        PassLaunch q[PLAN_MAX_VARIANTS];
+        const int n = plan_pass(pl, t, start_gen, size, known, counted, q);
+        for (int i = 0; i < n; ++i)
+            if (int rc = launch(q[i].var, size, q[i].sel_lo, q[i].sel_hi)) return rc;
+        return 0;
+    }
+    // behind the last launch: the kernels have re-armed the counters; the slot's event
+    int finish() {
+        s->counters_dirty[slot] = false;
+        if (!s->slot_event[slot]) HIP_TRY(hipEventCreateWithFlags(&s->slot_event[slot], hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(s->slot_event[slot], st));
+        s->slot_event_used[slot] = true;
+        return 0;
+    }
+};
 
 template <int D>
 int launch_solve(pikamd_solver* s, const pikamd_params* p, const ParamsK& pk, BatchRecord* batches, int n_batches,
@@ -282,230 +360,33 @@ int launch_solve(pikamd_solver* s, const pikamd_params* p, const ParamsK& pk, Ba
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    // memetic: groups of GS * LPE lanes per problem, one wavefront per workgroup, persistent waves
-    a.gs_log2 = pow2ceil_log2(pk.elites);
-    const int gs = 1 << a.gs_log2;
-    // species: pow2ceil(S) groups per problem share a wavefront and park / resume together
-    const int S = p->memetic_num_threads > 1 ? p->memetic_num_threads : 1;
-    a.species = S;
-    a.sp_log2 = pow2ceil_log2(S);
-    Schedule sc;
-    make_schedule(s, pk, gs, S, sc);
-    // Regime.  More lanes per elite buy latency with throughput (a problem-generation costs 31 us of
-    // SIMD time at one lane per elite, 68 / 95 / 158 us at 4 / 8 / 16): right when the chip would
-    // otherwise idle behind this call's long-running problems, wrong when other calls are queued up
-    // to use it.  Measured (512 x 4096-problem steps in pools of 64): 2 calls in flight 4.14 (adaptive)
-    // vs 3.84 M solves/s (one lane per elite everywhere), 4 calls in flight 4.32 vs 4.69.  So: with
-    // three or more OTHER calls of this handle still in flight, every pass uses one lane per elite.
-    bool throughput_regime = false;
-    {
-        int others = 0;
-        for (int k = 0; k < N_DEVICE_SLOTS + N_HOST_JOBS; ++k)
-            if (k != slot && s->slot_event_used[k] && hipEventQuery(s->slot_event[k]) == hipErrorNotReady) ++others;
-        (void)hipGetLastError(); // (hipErrorNotReady is an answer, not a failure)
-        throughput_regime = others >= 3;
-        if (s->opt.regime != 0) throughput_regime = s->opt.regime == 2; // forced (option "regime")
-    }
-    // ... and a call with the chip to itself takes the two-per-SIMD variant of the one-lane kernel only when
-    // its wavefronts outnumber the SIMDs (measured on the driver's 20-batch pool: threshold 5/8 -> 9/8 of
-    // the SIMD count: 2.85 -> 2.90 M solves/s; with other calls queued up the lower threshold stays)
-    if (!throughput_regime && s->opt.two_per_simd < 2 && !s->opt.force_occ2) sc.occ2_from = (long long)s->num_cu * 4 * 9 / 8;
-    int n_marks = sc.n_marks;
-    // A call whose problems each get a wavefront of the widest variant in one round gains nothing from
-    // compaction (there is nothing to re-pack into): one launch, no passes -- 3-6 % off the latency of
-    // the plugin-style calls (B = 1 .. 256).  Not in the throughput regime, where the one-lane
-    // wavefronts hold 16 problems each and re-packing is what keeps them full.
-    if (!reserve_only && !throughput_regime && sc.n_sched == 0 && !s->opt.passes_set) {
-        int widest = 1;
-        for (int l : {16, 8, 4, 2})
-            if (widest == 1 && lpe_allowed(s, l, gs, S, s->n_tips > 1)) widest = l;
-        if (widest > 1 && B <= (long long)s->num_cu * 4 * (WAVE / (gs * widest * (1 << a.sp_log2)))) n_marks = 0;
-    }
-    // per-slot scratch: parked state (one record per problem and species), two survivor lists
-    const long long cap = B;
-    const size_t recs = (size_t)B * (size_t)S;
-    const size_t d_rows = (size_t)StateRows<D>::D_ROWS(pk.elites);
-    const size_t off_d = 0;
-    const size_t off_l = off_d + sizeof(double) * d_rows * recs;
-    const size_t off_i = off_l + sizeof(long long) * StateRows<D>::L_ROWS * recs;
-    const size_t off_list = off_i + sizeof(int) * StateRows<D>::I_ROWS * recs;
-    const size_t off_cnt = off_list + sizeof(int) * 2 * (size_t)cap;
-    // stored population for chains with unbounded variables: 2 parities x (P fitness + P*D genes +
-    // P ints order) per problem
-    const bool has_unbounded = s->chain.bounded_mask != ((1u << s->chain.dof) - 1u);
-    const size_t pop_stride = (size_t)pk.population * (1 + D) + ((size_t)pk.population + 1) / 2;
-    const size_t off_pop = (off_cnt + 64 + 63) / 64 * 64;
-    const size_t total = off_pop + (has_unbounded ? sizeof(double) * 2 * pop_stride * (size_t)cap * (size_t)S : 0);
-    if (n_marks > 0 || has_unbounded) {
-        if (int rc = s->slot_state[slot].ensure(total)) return rc;
+    // memetic: groups of GS * LPE lanes per problem, one wavefront per workgroup, persistent waves.  The host's rule:
+    // the regime is the one at the time of the call, the first pass knows its size and is one launch, every later
+    // pass enqueues each variant the call's problems can reach and the variants select themselves by the count.
+    MemeticCall<D> m(s, p, pk, st, slot, a);
+    m.kc = kc;
+    const bool throughput_regime = plan_throughput(s, others_busy(s, slot));
+    int marks[16];
+    const int n_marks = plan_marks(s, m.pl, throughput_regime, B, false, marks);
+    const MemeticScratch lay = m.scratch(pk, B);
+    // (a reservation is for calls in either regime: as if the call had every pass of the schedule)
+    if (n_marks > 0 || lay.has_unbounded || (reserve_only && m.pl.sc.n_marks > 0)) {
+        if (int rc = s->slot_state[slot].ensure(lay.total)) return rc;
     }
     if (reserve_only) return 0;
-    if (int rc = upload_batch_table(s, batches, n_batches, st, &a.batches, &a.B, table)) return rc;
-    char* base = (char*)s->slot_state[slot].p;
-    a.pop = has_unbounded ? (double*)(base + off_pop) : nullptr;
-    a.pop_stride = (long long)pop_stride;
-    a.cap = cap;
-    a.st_d = n_marks ? (double*)(base + off_d) : nullptr;
-    a.st_l = n_marks ? (long long*)(base + off_l) : nullptr;
-    a.st_i = n_marks ? (int*)(base + off_i) : nullptr;
-    int* lists[2] = {n_marks ? (int*)(base + off_list) : nullptr, n_marks ? (int*)(base + off_list) + cap : nullptr};
-    unsigned char* cblk = s->counters + COUNTER_BLOCK * (size_t)slot;
-    unsigned long long* c_work = (unsigned long long*)cblk;
-    unsigned* c_nlist = (unsigned*)(cblk + 128);
-    unsigned* c_done = (unsigned*)(cblk + 256);
-    if (s->counters_dirty[slot]) HIP_TRY(hipMemsetAsync(cblk, 0, COUNTER_BLOCK, st)); // after a failed launch
+    if (int rc = upload_batch_table(s, batches, n_batches, st, &m.a.batches, &m.a.B, table)) return rc;
+    m.bind(lay, n_marks > 0);
+    if (s->counters_dirty[slot]) HIP_TRY(hipMemsetAsync(m.cblk, 0, COUNTER_BLOCK, st)); // after a failed launch
     s->counters_dirty[slot] = true;
-
-    // waves per CU of each kernel variant: asked once per handle and FLAVOUR (the general and the exact kernels are
-    // different code with different register counts: a handle switched between them by the option "arithmetic"
-    // must not size one flavour's grids by the other's figure)
-#define PIK_OCC_ROW (PIK_COMMON ? (PIK_NO_GOALS ? 1 : 2) : (PIK_XF ? 3 : 0))
-    auto capacity_of = [&](auto kernel, int variant, long long* cap_out) -> int {
-        int per_cu = s->occupancy_cache[PIK_OCC_ROW][variant];
-        if (per_cu == 0) {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, WAVE, 0));
-            if (per_cu < 1) per_cu = 1;
-            s->occupancy_cache[PIK_OCC_ROW][variant] = per_cu;
-        }
-        *cap_out = (long long)s->num_cu * per_cu;
-        return 0;
-    };
-    // one kernel variant: lanes per elite, wavefronts per SIMD it is compiled for
-    struct Variant {
-        int lpe, id;
-        long long capacity;  // wavefronts the chip holds of it
-        long long hi;        // largest problem count it is chosen for (adaptive schedule)
-    };
-    Variant var[8];
-    int n_var = 0;
-    auto add_variant = [&](auto kernel, int lpe_, int id) -> int {
-        Variant v{lpe_, id, 0, 0};
-        if (int rc = capacity_of(kernel, id, &v.capacity)) return rc;
-        var[n_var++] = v;
-        return 0;
-    };
-    auto launch_variant = [&](const Variant& v, unsigned lo, unsigned hi) -> int {
-        const long long groups_per_wave = WAVE / (gs * v.lpe * (1 << a.sp_log2));
-        const long long waves_needed = (a.B + groups_per_wave - 1) / groups_per_wave;
-        const long long grid = waves_needed < v.capacity ? waves_needed : v.capacity;
-        a.sel_lo = lo;
-        a.sel_hi = hi;
-        const dim3 g((unsigned)grid), b(WAVE);
-        switch (v.id) {
-            case 5: hipLaunchKernelGGL((memetic_kernel<D, 16>), g, b, 0, st, kc, a); break;
-            case 4: hipLaunchKernelGGL((memetic_kernel<D, 8>), g, b, 0, st, kc, a); break;
-            case 3: hipLaunchKernelGGL((memetic_kernel<D, 4>), g, b, 0, st, kc, a); break;
-            case 2: hipLaunchKernelGGL((memetic_kernel<D, 2>), g, b, 0, st, kc, a); break;
-            case 7:
-                if constexpr (D <= 9) hipLaunchKernelGGL((memetic_kernel<D, 1, false, 2>), g, b, 0, st, kc, a);
-                break;
-#if !defined(PIK_STRICT)
-            case 10: hipLaunchKernelGGL((memetic_kernel<D, 16, true>), g, b, 0, st, kc, a); break;
-            case 9: hipLaunchKernelGGL((memetic_kernel<D, 8, true>), g, b, 0, st, kc, a); break;
-#endif
-            case 8: hipLaunchKernelGGL((memetic_kernel<D, 2, true>), g, b, 0, st, kc, a); break;
-            case 6: hipLaunchKernelGGL((memetic_kernel<D, 1, true>), g, b, 0, st, kc, a); break;
-            default: hipLaunchKernelGGL((memetic_kernel<D, 1>), g, b, 0, st, kc, a); break;
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
-    };
-    // candidate variants, widest first.  Adaptive rule: a pass runs with the MOST lanes per elite
-    // whose wavefronts still fit the chip in one round for the problems it has (fewest generations'
-    // latency without queueing); the one-lane variant takes everything larger, compiled for two
-    // wavefronts per SIMD from the measured crossover on.
-    const bool multi = s->n_tips > 1;
-    const long long occ2_from_problems = sc.occ2_from * WAVE / gs; // first-pass wavefronts -> problems
-    if (multi) {
-#if !defined(PIK_STRICT)
-        if (!throughput_regime || sc.n_sched > 0) {
-            if (lpe_allowed(s, 16, gs, S, multi))
-                if (int rc = add_variant(memetic_kernel<D, 16, true>, 16, 10)) return rc;
-            if (lpe_allowed(s, 8, gs, S, multi))
-                if (int rc = add_variant(memetic_kernel<D, 8, true>, 8, 9)) return rc;
-        }
-#endif
-        if (!throughput_regime || sc.n_sched > 0)
-            if (lpe_allowed(s, 2, gs, S, multi))
-                if (int rc = add_variant(memetic_kernel<D, 2, true>, 2, 8)) return rc;
-        if (int rc = add_variant(memetic_kernel<D, 1, true>, 1, 6)) return rc;
-    } else {
-        const bool wide_ok = !throughput_regime || sc.n_sched > 0; // (a forced schedule may ask for any)
-        if (wide_ok && lpe_allowed(s, 16, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 16>, 16, 5)) return rc;
-        if (wide_ok && lpe_allowed(s, 8, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 8>, 8, 4)) return rc;
-        if (wide_ok && lpe_allowed(s, 4, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 4>, 4, 3)) return rc;
-        if (wide_ok && lpe_allowed(s, 2, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 2>, 2, 2)) return rc;
-        if (int rc = add_variant(memetic_kernel<D, 1>, 1, 1)) return rc;
-        if constexpr (D <= 9) {
-            // (its LDS footprint, 6 D rows, lets 5..8 wavefronts share a CU up to D = 9; beyond that
-            //  the register cap would cost scratch traffic for nothing.  The exact flavours have it too: their
-            //  descent and evaluations are calls that need fewer than 256 registers, and a second wavefront per
-            //  SIMD hides the latencies a lone one waits out)
-            bool occ2 = sc.occ2_ok && !(disabled_lanes_of(s, EXACT_FLAVOUR) & 1u);
-#if defined(PIK_STRICT)
-            occ2 = occ2 && s->chain.float_mask == 0u && s->chain.n_mimic == 0; // (a floating or a mimic joint: the literal descent, one per SIMD only)
-#endif
-            if (occ2)
-                if (int rc = add_variant(memetic_kernel<D, 1, false, 2>, 1, 7)) return rc;
-        }
-    }
-    for (int i = 0; i < n_var; ++i) {
-        const long long per_wave = WAVE / (gs * var[i].lpe * (1 << a.sp_log2));
-        var[i].hi = (var[i].lpe > 1) ? (long long)s->num_cu * 4 * per_wave // one wavefront per SIMD
-                    : (var[i].id == 7 || i == n_var - 1) ? 0xffffffffll
-                                                         : occ2_from_problems - 1;
-    }
+    plan_candidates(s, m.pl, !throughput_regime || m.pl.sc.n_sched > 0, D <= 9);
+    RangeTable t;
+    plan_ranges(s, m.pl, throughput_regime, t);
+    if (int rc = m.capacities()) return rc;
     for (int k = 0; k <= n_marks; ++k) {
-        a.fresh = (k == 0);
-        a.pause_gen = (k < n_marks) ? sc.marks[k] : 0x7fffffff;
-        a.list_in = (k == 0) ? nullptr : lists[(k - 1) & 1];
-        a.n_in = (k == 0) ? nullptr : c_nlist + k;
-        a.list_out = n_marks ? lists[k & 1] : nullptr;
-        a.n_out = n_marks ? c_nlist + (k + 1) : nullptr;
-        a.work_counter = c_work + k;
-        a.done = c_done + k;
-        const int start_gen = (k == 0) ? 0 : sc.marks[k - 1];
-        if (sc.n_sched > 0) {
-            // forced lanes per elite
-            int lpe_k = sc.lpe_of[0];
-            for (int i = 1; i < sc.n_sched; ++i)
-                if (start_gen >= sc.lpe_from[i]) lpe_k = sc.lpe_of[i];
-            int pick = -1;
-            for (int i = 0; i < n_var && pick < 0; ++i)
-                if (var[i].lpe == lpe_k) pick = i; // (one lane per elite: the one-per-SIMD build comes first)
-            if (pick < 0) pick = n_var - 1;
-            // one lane per elite and a call that fills the chip: the two-per-SIMD build
-            if (var[pick].lpe == 1 && var[n_var - 1].id == 7 && a.B >= occ2_from_problems) pick = n_var - 1;
-            if (int rc = launch_variant(var[pick], 0u, 0xffffffffu)) return rc;
-            continue;
-        }
-        // adaptive: variant i serves problem counts in (hi of the next wider one, its own hi]
-        long long lo = 0;
-        for (int i = 0; i < n_var; ++i) {
-            const long long hi = var[i].hi < lo ? lo : var[i].hi;
-            if (k == 0) {
-                // the first pass knows its size: one launch
-                if (a.B > lo && a.B <= hi) {
-                    if (int rc = launch_variant(var[i], 0u, 0xffffffffu)) return rc;
-                    break;
-                }
-            } else if (a.B > lo && hi > lo) {
-                // (a pass cannot have more survivors than the call has problems: narrower variants
-                //  whose range starts beyond that are not enqueued)
-                if (int rc = launch_variant(var[i], (unsigned)lo, (unsigned)(hi > 0xffffffffll ? 0xffffffffll : hi))) return rc;
-            }
-            lo = hi;
-        }
+        m.pass(k, marks, n_marks);
+        if (int rc = m.launch_pass(t, k == 0 ? 0 : marks[k - 1], m.a.B, k == 0 ? m.a.B : 0, k > 0)) return rc;
     }
-    s->counters_dirty[slot] = false;
-    if (!s->slot_event[slot]) HIP_TRY(hipEventCreateWithFlags(&s->slot_event[slot], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(s->slot_event[slot], st));
-    s->slot_event_used[slot] = true;
-    return 0;
+    return m.finish();
 }
 
 template <int D>

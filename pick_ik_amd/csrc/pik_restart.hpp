@@ -4,7 +4,8 @@
 // searchPositionIK (src/pick_ik_plugin.cpp:145-291) solves, and when no solution came back draws a random valid
 // configuration and solves again from there.  Attempt 0 of a call is the existing launch of pikamd_solve_batches
 // (launch_solve or the routed launcher), with a batch table whose guess is the slot's guess buffer and whose outputs
-// are the slot's attempt rows.  An attempt a >= 1 (launch_restart_attempt) is launch_solve's pass loop again with a
+// are the slot's attempt rows.  An attempt a >= 1 (launch_restart_attempt) is launch_solve's plan and pass loop (the
+// shared pik_memetic_plan.hpp and MemeticCall of pik_launch.hpp, not a copy) with a
 // first pass the two existing launchers never enqueue: fresh = 1 AND list_in = the problems still open, n_in = their
 // device-side number.  memetic_kernel already serves that combination (it reads `prob` from list_in, its size from
 // *n_in, starts from the batch's guess when `fresh`, picks its variant by sel_lo < *n_in <= sel_hi and re-arms
@@ -181,40 +182,18 @@ int launch_restart_gate(pikamd_solver* s, const ParamsK& pk, const RestartArgs& 
     return 0;
 }
 
-// launch_solve's per-slot scratch for a memetic call of B problems
-template <int D>
-struct RestartScratch {
-    size_t off_d, off_l, off_i, off_list, off_pop, pop_stride, total;
-    bool has_unbounded;
-    RestartScratch(const pikamd_solver* s, const ParamsK& pk, long long B, int S) {
-        const size_t recs = (size_t)B * (size_t)S;
-        const size_t d_rows = (size_t)StateRows<D>::D_ROWS(pk.elites);
-        off_d = 0;
-        off_l = off_d + sizeof(double) * d_rows * recs;
-        off_i = off_l + sizeof(long long) * StateRows<D>::L_ROWS * recs;
-        off_list = off_i + sizeof(int) * StateRows<D>::I_ROWS * recs;
-        const size_t off_cnt = off_list + sizeof(int) * 2 * (size_t)B;
-        has_unbounded = s->chain.bounded_mask != ((1u << s->chain.dof) - 1u);
-        pop_stride = (size_t)pk.population * (1 + D) + ((size_t)pk.population + 1) / 2;
-        off_pop = (off_cnt + 64 + 63) / 64 * 64;
-        total = off_pop + (has_unbounded ? sizeof(double) * 2 * pop_stride * (size_t)B * (size_t)S : 0);
-    }
-};
-
+// the slot's solver scratch for a call of B problems, in front of attempt 0: no attempt grows it under kernels in flight
 template <int D>
 int restart_reserve(pikamd_solver* s, const pikamd_params* p, const ParamsK& pk, long long B, int slot) {
     if (B == 0) return 0;
     const int S = p->memetic_num_threads > 1 ? p->memetic_num_threads : 1;
-    const RestartScratch<D> sc(s, pk, B, S);
-    return s->slot_state[slot].ensure(sc.total);
+    return s->slot_state[slot].ensure(memetic_scratch<D>(s, pk, B, S).total);
 }
 
-// The passes of a restart attempt when the option "passes" is not set: two of launch_solve's default marks.  The
-// problems of a restart attempt are the few a whole solve has failed on; what a pass re-packs is the tail of a tail,
-// and every mark costs an empty dispatch per candidate variant when nothing is left.  (Scheduling: no result
-// depends on the marks.)
-inline bool restart_default_mark(int generation) { return generation == 8 || generation == 32; }
-
+// Attempt a >= 1: the shared plan and launches of a memetic call (pik_memetic_plan.hpp, MemeticCall of pik_launch.hpp)
+// with what only a restart attempt has -- pass 0 starts from the device-side list of the open problems, a fresh start
+// each; the grids are sized for the n_hint problems the host knows to be open (n_hint < 0: it does not know, B);
+// the marks are the restart filter's; dirty counters are refused, because the open count in n_list[0] goes with them.
 template <int D>
 int launch_restart_attempt(pikamd_solver* s, const pikamd_params* p, const ParamsK& pk, BatchRecord* rec,
                            unsigned long long rng_seed_a, const int* list, long long n_hint, hipStream_t st, int slot) {
@@ -230,184 +209,35 @@ int launch_restart_attempt(pikamd_solver* s, const pikamd_params* p, const Param
     a.n_batches = 1;
     a.rng_seed = rng_seed_a;
     a.B = B;
-    a.gs_log2 = pow2ceil_log2(pk.elites);
-    const int gs = 1 << a.gs_log2;
-    const int S = p->memetic_num_threads > 1 ? p->memetic_num_threads : 1;
-    a.species = S;
-    a.sp_log2 = pow2ceil_log2(S);
-    const bool multi = s->n_tips > 1;
-    Schedule sc;
-    make_schedule(s, pk, gs, S, sc);
-    // the regime: launch_solve's rule
-    bool throughput_regime = false;
-    {
-        int others = 0;
-        for (int k = 0; k < N_DEVICE_SLOTS + N_HOST_JOBS; ++k)
-            if (k != slot && s->slot_event_used[k] && hipEventQuery(s->slot_event[k]) == hipErrorNotReady) ++others;
-        (void)hipGetLastError(); // (hipErrorNotReady is an answer, not a failure)
-        throughput_regime = others >= 3;
-        if (s->opt.regime != 0) throughput_regime = s->opt.regime == 2;
-    }
-    if (!throughput_regime && s->opt.two_per_simd < 2 && !s->opt.force_occ2) sc.occ2_from = (long long)s->num_cu * 4 * 9 / 8;
-    int marks[16], n_marks = 0;
-    for (int i = 0; i < sc.n_marks; ++i)
-        if (s->opt.passes_set || restart_default_mark(sc.marks[i])) marks[n_marks++] = sc.marks[i];
-    if (!throughput_regime && sc.n_sched == 0 && !s->opt.passes_set) {
-        int widest = 1;
-        for (int l : {16, 8, 4, 2})
-            if (widest == 1 && lpe_allowed(s, l, gs, S, multi)) widest = l;
-        if (widest > 1 && Bh <= (long long)s->num_cu * 4 * (WAVE / (gs * widest * (1 << a.sp_log2)))) n_marks = 0;
-    }
-    const RestartScratch<D> lay(s, pk, B, S);
+    MemeticCall<D> m(s, p, pk, st, slot, a);
+    m.kc = kc;
+    const bool throughput_regime = plan_throughput(s, others_busy(s, slot));
+    int marks[16];
+    const int n_marks = plan_marks(s, m.pl, throughput_regime, Bh, true, marks);
+    const MemeticScratch lay = m.scratch(pk, B);
     if (n_marks > 0 || lay.has_unbounded) {
         if (int rc = s->slot_state[slot].ensure(lay.total)) return rc; // (restart_reserve has: nothing grows here)
     }
-    if (int rc = upload_batch_table(s, rec, 1, st, &a.batches, &a.B, table)) return rc;
-    char* base = (char*)s->slot_state[slot].p;
-    a.pop = lay.has_unbounded ? (double*)(base + lay.off_pop) : nullptr;
-    a.pop_stride = (long long)lay.pop_stride;
-    a.cap = B;
-    a.st_d = n_marks ? (double*)(base + lay.off_d) : nullptr;
-    a.st_l = n_marks ? (long long*)(base + lay.off_l) : nullptr;
-    a.st_i = n_marks ? (int*)(base + lay.off_i) : nullptr;
-    int* lists[2] = {n_marks ? (int*)(base + lay.off_list) : nullptr, n_marks ? (int*)(base + lay.off_list) + B : nullptr};
-    unsigned char* cblk = s->counters + COUNTER_BLOCK * (size_t)slot;
-    unsigned long long* c_work = (unsigned long long*)cblk;
-    unsigned* c_nlist = (unsigned*)(cblk + 128);
-    unsigned* c_done = (unsigned*)(cblk + 256);
+    if (int rc = upload_batch_table(s, rec, 1, st, &m.a.batches, &m.a.B, table)) return rc;
+    m.bind(lay, n_marks > 0);
     // (a failed launch leaves the slot's counters dirty; the open count in n_list[0] goes with them, so the caller
     //  gives the call up)
     if (s->counters_dirty[slot]) return fail(PIKAMD_EHIP, "restart attempt: an earlier launch on slot %d failed", slot);
     s->counters_dirty[slot] = true;
-
-    auto capacity_of = [&](auto kernel, int variant, long long* cap_out) -> int {
-        int per_cu = s->occupancy_cache[PIK_OCC_ROW][variant];
-        if (per_cu == 0) {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, WAVE, 0));
-            if (per_cu < 1) per_cu = 1;
-            s->occupancy_cache[PIK_OCC_ROW][variant] = per_cu;
-        }
-        *cap_out = (long long)s->num_cu * per_cu;
-        return 0;
-    };
-    struct Variant {
-        int lpe, id;
-        long long capacity; // wavefronts the chip holds of it
-        long long hi;       // largest problem count it is chosen for (adaptive schedule)
-    };
-    Variant var[8];
-    int n_var = 0;
-    auto add_variant = [&](auto kernel, int lpe_, int id) -> int {
-        Variant v{lpe_, id, 0, 0};
-        if (int rc = capacity_of(kernel, id, &v.capacity)) return rc;
-        var[n_var++] = v;
-        return 0;
-    };
-    auto launch_variant = [&](const Variant& v, unsigned lo, unsigned hi) -> int {
-        const long long groups_per_wave = WAVE / (gs * v.lpe * (1 << a.sp_log2));
-        const long long waves_needed = (Bh + groups_per_wave - 1) / groups_per_wave;
-        const long long grid = waves_needed < v.capacity ? waves_needed : v.capacity;
-        a.sel_lo = lo;
-        a.sel_hi = hi;
-        const dim3 g((unsigned)grid), b(WAVE);
-        switch (v.id) {
-            case 5: hipLaunchKernelGGL((memetic_kernel<D, 16>), g, b, 0, st, kc, a); break;
-            case 4: hipLaunchKernelGGL((memetic_kernel<D, 8>), g, b, 0, st, kc, a); break;
-            case 3: hipLaunchKernelGGL((memetic_kernel<D, 4>), g, b, 0, st, kc, a); break;
-            case 2: hipLaunchKernelGGL((memetic_kernel<D, 2>), g, b, 0, st, kc, a); break;
-            case 7:
-                if constexpr (D <= 9) hipLaunchKernelGGL((memetic_kernel<D, 1, false, 2>), g, b, 0, st, kc, a);
-                break;
-#if !defined(PIK_STRICT)
-            case 10: hipLaunchKernelGGL((memetic_kernel<D, 16, true>), g, b, 0, st, kc, a); break;
-            case 9: hipLaunchKernelGGL((memetic_kernel<D, 8, true>), g, b, 0, st, kc, a); break;
-#endif
-            case 8: hipLaunchKernelGGL((memetic_kernel<D, 2, true>), g, b, 0, st, kc, a); break;
-            case 6: hipLaunchKernelGGL((memetic_kernel<D, 1, true>), g, b, 0, st, kc, a); break;
-            default: hipLaunchKernelGGL((memetic_kernel<D, 1>), g, b, 0, st, kc, a); break;
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
-    };
-    // launch_solve's candidates and range table
-    const long long occ2_from_problems = sc.occ2_from * WAVE / gs;
-    const bool wide_ok = !throughput_regime || sc.n_sched > 0;
-    if (multi) {
-#if !defined(PIK_STRICT)
-        if (wide_ok && lpe_allowed(s, 16, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 16, true>, 16, 10)) return rc;
-        if (wide_ok && lpe_allowed(s, 8, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 8, true>, 8, 9)) return rc;
-#endif
-        if (wide_ok && lpe_allowed(s, 2, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 2, true>, 2, 8)) return rc;
-        if (int rc = add_variant(memetic_kernel<D, 1, true>, 1, 6)) return rc;
-    } else {
-        if (wide_ok && lpe_allowed(s, 16, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 16>, 16, 5)) return rc;
-        if (wide_ok && lpe_allowed(s, 8, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 8>, 8, 4)) return rc;
-        if (wide_ok && lpe_allowed(s, 4, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 4>, 4, 3)) return rc;
-        if (wide_ok && lpe_allowed(s, 2, gs, S, multi))
-            if (int rc = add_variant(memetic_kernel<D, 2>, 2, 2)) return rc;
-        if (int rc = add_variant(memetic_kernel<D, 1>, 1, 1)) return rc;
-        if constexpr (D <= 9) {
-            bool occ2 = sc.occ2_ok && !(disabled_lanes_of(s, EXACT_FLAVOUR) & 1u);
-#if defined(PIK_STRICT)
-            occ2 = occ2 && s->chain.float_mask == 0u && s->chain.n_mimic == 0;
-#endif
-            if (occ2)
-                if (int rc = add_variant(memetic_kernel<D, 1, false, 2>, 1, 7)) return rc;
-        }
-    }
-    for (int i = 0; i < n_var; ++i) {
-        const long long per_wave = WAVE / (gs * var[i].lpe * (1 << a.sp_log2));
-        var[i].hi = (var[i].lpe > 1) ? (long long)s->num_cu * 4 * per_wave // one wavefront per SIMD
-                    : (var[i].id == 7 || i == n_var - 1) ? 0xffffffffll
-                                                         : occ2_from_problems - 1;
-    }
+    plan_candidates(s, m.pl, !throughput_regime || m.pl.sc.n_sched > 0, D <= 9);
+    RangeTable t;
+    plan_ranges(s, m.pl, throughput_regime, t);
+    if (int rc = m.capacities()) return rc;
     for (int k = 0; k <= n_marks; ++k) {
-        // every pass starts from a device-side list: pass 0 from the open problems, a fresh start each
-        a.fresh = (k == 0);
-        a.pause_gen = (k < n_marks) ? marks[k] : 0x7fffffff;
-        a.list_in = (k == 0) ? list : lists[(k - 1) & 1];
-        a.n_in = c_nlist + k;
-        a.list_out = n_marks ? lists[k & 1] : nullptr;
-        a.n_out = n_marks ? c_nlist + (k + 1) : nullptr;
-        a.work_counter = c_work + k;
-        a.done = c_done + k;
-        const int start_gen = (k == 0) ? 0 : marks[k - 1];
-        if (sc.n_sched > 0) {
-            // forced lanes per elite
-            int lpe_k = sc.lpe_of[0];
-            for (int i = 1; i < sc.n_sched; ++i)
-                if (start_gen >= sc.lpe_from[i]) lpe_k = sc.lpe_of[i];
-            int pick = -1;
-            for (int i = 0; i < n_var && pick < 0; ++i)
-                if (var[i].lpe == lpe_k) pick = i;
-            if (pick < 0) pick = n_var - 1;
-            if (var[pick].lpe == 1 && var[n_var - 1].id == 7 && Bh >= occ2_from_problems) pick = n_var - 1;
-            if (int rc = launch_variant(var[pick], 0u, 0xffffffffu)) return rc;
-            continue;
+        m.pass(k, marks, n_marks);
+        if (k == 0) {
+            m.a.list_in = list;
+            m.a.n_in = m.c_nlist;
         }
-        // adaptive: variant i serves problem counts in (hi of the next wider one, its own hi]; a pass cannot have
-        // more problems than the attempt, and where the host knows the attempt's size pass 0 is one launch
-        long long lo = 0;
-        for (int i = 0; i < n_var; ++i) {
-            const long long hi = var[i].hi < lo ? lo : var[i].hi;
-            const bool reachable = Bh > lo && hi > lo;
-            const bool exact_size = k == 0 && n_hint > 0;
-            if (reachable && (!exact_size || n_hint <= hi))
-                if (int rc = launch_variant(var[i], (unsigned)lo, (unsigned)(hi > 0xffffffffll ? 0xffffffffll : hi))) return rc;
-            lo = hi;
-        }
+        // (where the host knows the attempt's size pass 0 is one launch)
+        if (int rc = m.launch_pass(t, k == 0 ? 0 : marks[k - 1], Bh, (k == 0 && n_hint > 0) ? n_hint : 0, true)) return rc;
     }
-    s->counters_dirty[slot] = false;
-    if (!s->slot_event[slot]) HIP_TRY(hipEventCreateWithFlags(&s->slot_event[slot], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(s->slot_event[slot], st));
-    s->slot_event_used[slot] = true;
-    return 0;
+    return m.finish();
 }
 
 template <int D>

@@ -31,6 +31,30 @@ def test_every_flavour_has_a_source_hash():
     assert all(len(v) == 16 for v in shas.values()) and len(set(shas.values())) == len(shas)
 
 
+def test_the_headers_the_source_hash_leaves_out_hold_no_device_code():
+    """flavour_sha is the hash of the DEVICE source: it skips the launcher headers, which must therefore define no
+    kernel, device function, constant or LDS variable -- a kernel cannot hide from the hash in them"""
+    assert B.HOST_LAUNCH_HEADERS == ("pik_launch.hpp", "pik_memetic_plan.hpp")
+    inst = {os.path.basename(f) for f in B._deps("pik_inst.hip", True)}
+    for name in B.HOST_LAUNCH_HEADERS:
+        assert name in inst, name
+        code = B._strip_comments(open(os.path.join(B.CSRC, name)).read())
+        for word in ("__global__", "__device__", "__constant__", "__shared__"):
+            assert word not in code, (name, word)
+
+
+def test_memetic_plan_is_the_three_launchers_rules(tmp_path):
+    """tests/native/memetic_plan_check.cpp: the plan as a host-only program, held to hand-computed schedules"""
+    import subprocess
+    exe = str(tmp_path / "memetic_plan_check")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "native", "memetic_plan_check.cpp")
+    r = subprocess.run([B.hipcc(), "-x", "hip", "--cuda-host-only", "-std=c++17", src, "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "memetic plan check OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 #: the link list of the two libraries: blocks of (build directory, object stem), each one object per chain length
 PRODUCT_BLOCKS = [("fast", "pik_inst"), ("exact", "pik_inst"), ("common", "pik_inst"), ("common_goals", "pik_inst"),
                   ("fast", "pik_path_inst"), ("exact", "pik_path_inst"),

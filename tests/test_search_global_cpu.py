@@ -155,26 +155,37 @@ def test_restart_launcher_leaves_the_existing_translation_units_alone():
 
 def test_restart_scratch_is_launch_solves_layout():
     """The restart launcher sizes the slot's solver scratch itself, in front of attempt 0, so that no attempt grows it
-    under kernels in flight: every term of its layout must be the one launch_solve and the routed launcher write."""
+    under kernels in flight, and it is the layout launch_solve and the routed launcher use by construction: every term
+    of the layout is written in ONE file under csrc/, the plan header, and in none of the three launcher headers; the
+    record rows of a chain length (StateRows<D>, device side) are handed to it in one place, which all three call."""
     from pick_ik_amd import build as Bd
 
-    def text(name):
-        return Bd._strip_comments(open(os.path.join(Bd.CSRC, name)).read())
-
-    restart, launch, route = text("pik_restart.hpp"), text("pik_launch.hpp"), text("pik_route.hpp")
-    scratch = restart[restart.index("struct RestartScratch"):restart.index("int restart_reserve")]
-    terms = ("(size_t)B * (size_t)S", "(size_t)StateRows<D>::D_ROWS(pk.elites)", "sizeof(double) * d_rows * recs",
-             "sizeof(long long) * StateRows<D>::L_ROWS * recs", "sizeof(int) * StateRows<D>::I_ROWS * recs",
-             "s->chain.bounded_mask != ((1u << s->chain.dof) - 1u)",
-             "(size_t)pk.population * (1 + D) + ((size_t)pk.population + 1) / 2", "(off_cnt + 64 + 63) / 64 * 64")
+    text = {f: Bd._strip_comments(open(os.path.join(Bd.CSRC, f)).read()) for f in sorted(os.listdir(Bd.CSRC))}
+    launchers = ("pik_launch.hpp", "pik_route.hpp", "pik_restart.hpp")
+    terms = ("(size_t)B * (size_t)S", "sizeof(double) * d_rows * recs", "sizeof(long long) * l_rows * recs",
+             "sizeof(int) * i_rows * recs", "s->chain.bounded_mask != ((1u << s->chain.dof) - 1u)",
+             "(size_t)population * (1 + D) + ((size_t)population + 1) / 2", "(off_cnt + 64 + 63) / 64 * 64",
+             # the two survivor lists and the stored population
+             "sizeof(int) * 2 * (size_t)B", "sizeof(double) * 2 * pop_stride * (size_t)B * (size_t)S")
     for t in terms:
-        assert t in scratch and t in launch and t in route, t
-    # the two survivor lists and the stored population, with launch_solve's cap = B
-    for a, b in (("sizeof(int) * 2 * (size_t)B", "sizeof(int) * 2 * (size_t)cap"),
-                 ("sizeof(double) * 2 * pop_stride * (size_t)B * (size_t)S",
-                  "sizeof(double) * 2 * pop_stride * (size_t)cap * (size_t)S")):
-        assert a in scratch and b in launch and b in route, a
-    assert "const long long cap = B;" in launch and "const long long cap = B;" in route
+        assert [f for f in text if t in text[f]] == ["pik_memetic_plan.hpp"], t
+    for name in ("off_d", "off_l", "off_i", "off_list", "off_pop", "pop_stride"):
+        assigned = re.compile(r"(?<![.\w])" + name + r" = ")  # (the launchers read the fields, none computes one)
+        assert assigned.search(text["pik_memetic_plan.hpp"]), name
+        assert not [f for f in launchers if assigned.search(text[f])], name
+    # the rows of a record: named once, in the function that makes the layout for a chain length ...
+    for rows in ("(size_t)StateRows<D>::D_ROWS(pk.elites)", "StateRows<D>::L_ROWS", "StateRows<D>::I_ROWS"):
+        assert [(f, text[f].count(rows)) for f in launchers if rows in text[f]] == [("pik_launch.hpp", 1)], rows
+    make = text["pik_launch.hpp"]
+    make = make[make.index("MemeticScratch memetic_scratch("):make.index("struct MemeticCall")]
+    assert all(rows in make for rows in ("D_ROWS(pk.elites)", "L_ROWS", "I_ROWS", "chain_has_unbounded(s)"))
+    # ... which the three launchers call (launch_solve and the routed one through MemeticCall::scratch), and nothing
+    # else makes one
+    assert text["pik_launch.hpp"].count("memetic_scratch<D>(") == 1 and "m.scratch(pk, B)" in text["pik_launch.hpp"]
+    assert "m.scratch(pk, B)" in text["pik_route.hpp"] and "memetic_scratch" not in text["pik_route.hpp"]
+    assert text["pik_restart.hpp"].count("memetic_scratch<D>(s, pk, B, S)") == 1 and "m.scratch(pk, B)" in text["pik_restart.hpp"]
+    assert [f for f in text if "MemeticScratch(" in text[f]] == ["pik_launch.hpp", "pik_memetic_plan.hpp"]
+    assert text["pik_launch.hpp"].count("MemeticScratch(") == 1
 
 
 def test_committed_ledger_has_the_restart_kernels_without_scratch_or_spill():
