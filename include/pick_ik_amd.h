@@ -642,6 +642,67 @@ typedef struct pikamd_gate {
 int32_t pikamd_gate_batch(pikamd_solver* s, const pikamd_params* p, const pikamd_gate* gate, int64_t n,
                           const double* goal_pos_quat, const double* seed, const double* q, int32_t* pass);
 int32_t pikamd_set_approximate_gate(pikamd_solver* s, const pikamd_gate* gate);
+/* ---- Cartesian paths from a pose: restart the start state until the path holds ----------------------
+ * A planner has a Cartesian motion (approach, retreat, straight-line segment) and a pose to start it from, but no
+ * joint state: it needs a start configuration from which the whole motion is feasible.  With the entry points above
+ * that is a host loop -- waypoint 0 with restarts, the path from its answer, a look at `reached`, another start when
+ * the path broke -- of up to 2 * max_attempts dependent launches, and the restart states are not the caller's to
+ * reproduce.  Here P paths of W waypoints and up to max_attempts attempts each run in ONE launch.  p->mode must be 1
+ * (local mode).  The result is DEFINED by the entry points above, bit for bit:
+ *
+ *   init[p] = initial_guess ? initial_guess[p] : seed[p]
+ *   if init[p] is invalid (a bounded variable outside its limits, or a NaN): init[p] = draw(p, 0, init[p])
+ *   best[p] = -1
+ *   for a in 0 .. max_attempts-1, for every p still open:
+ *     (sol0, st0, c0, stats0) = pikamd_solve_batch(local mode, goal[p][0], seed = seed[p], initial_guess = init[p])
+ *     rows_a = W rows:
+ *       row 0 = (st0 > 0 ? sol0 : seed[p], st0, c0, stats0)      (what the call returned; NO joint-step test here)
+ *       if st0 > 0 and W > 1: rows 1.. = pikamd_solve_paths(local mode, P = 1, W - 1, goal[p][1..], start = sol0,
+ *                                                           max_joint_step)
+ *       else:                 rows 1.. = (seed[p], PIKAMD_NOT_ATTEMPTED, 0, zero)
+ *     reached_a = st0 > 0 ? 1 + reached of that path call : 0
+ *     totals[p] += every stats row of rows_a, field by field;  attempts[p] = a + 1
+ *     if reached_a > best[p]: the outputs of p become rows_a; best[p] = reached_a      (first among equals wins)
+ *     if reached_a == W: p is closed     else: init[p] = draw(p, a + 1, init[p])
+ *   reached[p] = best[p]
+ *
+ * draw is exactly the draw of pikamd_search_batch above: Philox stream RESTART (= 3), key (rng_seed,
+ * problem_offset + p), every operation rounded on its own.  seed[p] stays the minimal-displacement reference of
+ * waypoint 0 and is what a failed waypoint 0 returns; from waypoint 1 on the previous answer is both the reference and
+ * the start, as in pikamd_solve_paths.  The handle's approximate-solution gate is NOT applied, as in
+ * pikamd_solve_paths.
+ *
+ * Consequences: W = 1 is pikamd_search_batch with no gate (stats[p][0] is the kept attempt's, totals[p] the sum
+ * pikamd_search_batch reports; a problem that no attempt solved keeps the row of its FIRST attempt, so its final_cost
+ * is the first attempt's where pikamd_search_batch reports the last one's).  max_attempts = 1 with a valid initial guess is one pikamd_solve_batch followed by one
+ * pikamd_solve_paths.  With return_approximate_solution set every waypoint is solved (st > 0), so only a refused jump
+ * reopens a path.  A batch cut into calls or shards with matching problem_offset gives the answers of one call.
+ *   goal_pos_quat [P][W][n_tips][7], seed [P][dof], initial_guess [P][dof] (NULL = seed), max_joint_step [dof] (may be
+ *   NULL), solution [P][W][dof], status [P][W], final_cost [P][W] (may be NULL), stats [P][W] (may be NULL),
+ *   reached [P] (may be NULL), attempts [P] (may be NULL), totals [P] (may be NULL).
+ * max_attempts is 1..PIKAMD_MAX_ATTEMPTS, W >= 1; P = 0 returns 0.  Not with the option joint_layout = soa.
+ * Not served (out of scope): global mode for waypoint 0; a parallel schedule over the attempts (attempt a + 1 depends
+ * on how far attempt a got); a relative (mean-step) jump threshold; all_* rows per attempt. */
+/* host pointers; synchronous, staged through the library's own pinned buffers and stream like pikamd_solve_batch,
+ * behind the same automatic self test of the local-mode kernels */
+int32_t pikamd_search_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                            const double* goal_pos_quat, const double* seed, const double* initial_guess,
+                            const double* max_joint_step, uint64_t rng_seed, int64_t problem_offset,
+                            int32_t max_attempts, double* solution, int32_t* status, double* final_cost,
+                            pikamd_stats* stats, int32_t* reached, int32_t* attempts, pikamd_stats* totals);
+/* device pointers (max_joint_step too); enqueues on `stream` and returns without synchronising, no self test (see
+ * pikamd_solve_batch_device for `slot`).  The rows of the attempts behind the first are kept in scratch that belongs
+ * to the handle's slot; it grows only when a call needs more than any earlier call on that slot did (a grow frees,
+ * and a free synchronises the device: run the largest call first where that matters). */
+int32_t pikamd_search_paths_device(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                   const double* d_goal_pos_quat, const double* d_seed,
+                                   const double* d_initial_guess, const double* d_max_joint_step, uint64_t rng_seed,
+                                   int64_t problem_offset, int32_t max_attempts, double* d_solution,
+                                   int32_t* d_status, double* d_final_cost, pikamd_stats* d_stats, int32_t* d_reached,
+                                   int32_t* d_attempts, pikamd_stats* d_totals, void* stream, int32_t slot);
+/* name of the kernel pikamd_search_paths* launches for P paths (see pikamd_kernel_name), e.g.
+ * `pik_exact::ik_startpath_team_kernel<7,16>` */
+const char* pikamd_search_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -6,7 +6,7 @@ and FLAVOUR, one object per supported chain length: the kernels are templates ov
 translation unit took 2.5 minutes, and the per-length objects build in parallel, only those whose inputs changed.
 Two tables say what there is -- FLAVOURS (build directory -> kernel namespace and flags) and FAMILIES (source file ->
 the flavours it is built for in each library) --, family_objects() expands one (family, flavour) over the lengths and
-library_objects() is the link list, in link order.  Objects live in pick_ik_amd/_build/ (git-ignored).
+library_objects() + link_objects() is the link list, in link order.  Objects live in pick_ik_amd/_build/ (git-ignored).
 """
 from __future__ import annotations
 
@@ -79,7 +79,11 @@ FAMILIES = {
     "pik_search_inst.hip": (("fast", "exact"), ("strict",)),
     "pik_route_inst.hip": (ROUTE_FLAVOURS, ()),
     "pik_restart_inst.hip": (ROUTE_FLAVOURS, ("strict",)),
+    "pik_startpath_inst.hip": (("fast", "exact"), ("strict",)),
 }
+#: the families behind the link list library_objects() gives (tests/test_build_cpu.py holds that list to the blocks it
+#: names, in their order): their objects are linked last, see link_objects()
+APPENDED_FAMILIES = ("pik_startpath_inst.hip",)
 
 
 def family_objects(family: str, flavour: str):
@@ -100,7 +104,18 @@ def library_objects(strict: bool):
             # (product library: the fused one, pik_exact_host_solve; verification library: its own, pik_strict_host_solve)
             (os.path.join(d, "pik_host_solve.o"), "pik_host_solve.hip", ["--cuda-host-only"] + ([] if strict else EXACT_FLAGS))]
     for family, flavours in FAMILIES.items():
+        if family in APPENDED_FAMILIES:
+            continue
         for flavour in flavours[1 if strict else 0]:
+            objs += family_objects(family, flavour)
+    return objs
+
+
+def link_objects(strict: bool):
+    """what one library is linked from: library_objects() and, behind them, the objects of APPENDED_FAMILIES"""
+    objs = library_objects(strict)
+    for family in APPENDED_FAMILIES:
+        for flavour in FAMILIES[family][1 if strict else 0]:
             objs += family_objects(family, flavour)
     return objs
 
@@ -216,8 +231,8 @@ def _lib_stamp(strict: bool) -> str:
     flags = _flavor_flags(strict) + ([] if strict else ["+exact:"] + EXACT_FLAGS + ["+common:"] + COMMON_FLAGS + ["+common_goals:"] + COMMON_GOALS_FLAGS)
     # (+paths: the waypoint-path objects are linked in -- a library from before them is not this one)
     # (+search: ... and the restart-search objects; +route: ... and, in the product library, the routed launcher's;
-    #  +restart: ... and the restart launcher's)
-    return _stamp(flags + ["+paths", "+search"] + ([] if strict else ["+route"]) + ["+restart"] + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
+    #  +restart: ... and the restart launcher's; +startpath: ... and the start-search path kernels')
+    return _stamp(flags + ["+paths", "+search"] + ([] if strict else ["+route"]) + ["+restart", "+startpath"] + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
 
 
 def is_stale(lib: str = LIB) -> bool:
@@ -330,7 +345,7 @@ def ledger_rows():
     compiler's resource remarks kept beside the objects; None when an object has none (not built here)"""
     from . import kernel_resources as KR
     rows = []
-    for o in library_objects(False) + library_objects(True):
+    for o in link_objects(False) + link_objects(True):
         res = o[0] + ".res"
         if o[1] not in FAMILIES:
             continue
@@ -376,7 +391,7 @@ def build_library(force: bool = False, verbose: bool = False, strict_too: bool =
     for lib, strict in flavors:
         if not (force or is_stale(lib) or os.environ.get("PIK_ONLY_D") or os.environ.get("PIK_EXTRA_HIPCC_FLAGS")):
             continue
-        objs = library_objects(strict)
+        objs = link_objects(strict)
         stale = [o for o in objs if force or _obj_stale(*o, _is_strict_obj(o))]
         jobs += [(o, _is_strict_obj(o)) for o in stale if (o, _is_strict_obj(o)) not in jobs]
         relink.append((lib, [o[0] for o in objs]))

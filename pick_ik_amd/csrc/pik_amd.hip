@@ -21,6 +21,7 @@
 #include "pik_route_ops.hpp"
 #include "pik_search_ops.hpp"
 #include "pik_solver.hpp"
+#include "pik_startpath_ops.hpp"
 #include "pik_urdf.hpp"
 
 namespace pik {
@@ -45,6 +46,7 @@ PIK_DECLARE_OPS_FAMILY(void, path)
 PIK_DECLARE_OPS_FAMILY(void, search)
 PIK_DECLARE_OPS_FAMILY(void, route)
 PIK_DECLARE_OPS_FAMILY(void, restart)
+PIK_DECLARE_OPS_FAMILY(void, startpath)
 } // namespace pik_exact
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
@@ -80,7 +82,7 @@ enum Flavour {
 #endif
     N_FLAVOURS
 };
-enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, N_FAMILIES };
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -104,6 +106,8 @@ struct SolverExt : pikamd_solver {
     pik::DevBuf gate_params_dev; // [N_SLOTS] ParamsK, GATE_PARAMS_STRIDE apart
     pik::ParamsK gate_params_host[pik::N_SLOTS];
     bool gate_params_valid[pik::N_SLOTS] = {};
+    // pikamd_search_paths*: per slot the rows of an attempt behind the first (pik_startpath.hpp)
+    pik::DevBuf startpath_rows[pik::N_SLOTS];
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -126,11 +130,12 @@ const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
 #else
      untyped<pik::RouteOps, pik::route_ops>,
 #endif
-     untyped<pik::RestartOps, pik::restart_ops>},
+     untyped<pik::RestartOps, pik::restart_ops>, untyped<pik::StartPathOps, pik::startpath_ops>},
 #if !defined(PIK_STRICT)
-    {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops},
-    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops},
-    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops},
+    {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops,
+     pik_exact::startpath_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr},
 #endif
 };
 // ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
@@ -272,6 +277,9 @@ const pik::PathOps* path_ops_of(const pikamd_solver* s, const pikamd_params* p) 
 }
 const pik::SearchOps* search_ops_of(const pikamd_solver* s, const pikamd_params* p) {
     return ops_at<pik::SearchOps>(flavour_of(s, p, nullptr), FAM_SEARCH, s->chain.dof);
+}
+const pik::StartPathOps* startpath_ops_of(const pikamd_solver* s, const pikamd_params* p) {
+    return ops_at<pik::StartPathOps>(flavour_of(s, p, nullptr), FAM_STARTPATH, s->chain.dof);
 }
 // ... and the restart launcher of a global-mode call (pik_restart.hpp), in the flavour solve_ops_of picks
 const pik::RestartOps* restart_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
@@ -498,6 +506,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : s->slot_soa) b.release();
     for (auto& b : ext_of(s)->search_rows) b.release();
     for (auto& b : ext_of(s)->restart_rows) b.release();
+    for (auto& b : ext_of(s)->startpath_rows) b.release();
     ext_of(s)->gate_params_dev.release();
     for (auto& j : s->jobs) {
         j.dev.release();
@@ -1412,6 +1421,8 @@ const CallKind SEARCH = {"pikamd_search_batch", 1, "restarts are served in local
                          ": a restart attempt of the memetic kernels would have to start a first pass from a device-side "
                          "list of the failed problems, which their launch does not offer",
                          false, "[B][dof]", "seed"};
+const CallKind SEARCH_PATHS = {"pikamd_search_paths", 1, "paths from a pose are searched in local mode (mode = 1)", "", true,
+                                 "[P][W][dof]", "seed"};
 const CallKind SEARCH_GLOBAL = {"pikamd_search_global_batch", 0, "restarts of the memetic solver (mode = 0)",
                                 ": local mode is served by pikamd_search_batch", false, "[B][dof]", "seed"};
 
@@ -1506,7 +1517,7 @@ class Staging {
     pikamd_solver* s_;
     const char* who_;
     pik::HostJob& J_;
-    Region r_[12];
+    Region r_[12]; // (pikamd_search_paths registers 11)
     int n_ = 0;
     size_t in_bytes_ = 0, total_ = 0;
 };
@@ -1597,6 +1608,130 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
     if (!s || !p) return "";
     const Flavour f = flavour_of(s, p, nullptr);
     return variant_name(s, f, "path", pik::path_lanes(s, P, is_exact(f)));
+}
+
+} // extern "C"
+
+// ---- Cartesian paths from a pose (pik_startpath.hpp) ------------------------------------------------
+namespace {
+
+// the arrays of a pikamd_search_paths call: host pointers, or device pointers
+struct StartPathArrays {
+    const double *goal, *seed, *guess, *max_step; // guess: null = the seed
+    double* solution;
+    int32_t* status;
+    double* cost;
+    pikamd_stats* stats;
+    int32_t *reached, *attempts;
+    pikamd_stats* totals;
+    bool required_null() const { return !goal || !seed || !solution || !status; }
+};
+
+// what both entry points refuse: check_call's list for a path call, then the attempts
+int check_search_paths(const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, int32_t K,
+                       const StartPathArrays& d, pik::ParamsK& pk) {
+    if (int rc = check_call(SEARCH_PATHS, s, p, P, W, d.required_null(), pk)) return rc;
+    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
+        return fail(PIKAMD_EINVAL, "%s: max_attempts %d: expected 1..%d", SEARCH_PATHS.name, (int)K, PIKAMD_MAX_ATTEMPTS);
+    return 0;
+}
+
+// The arguments of a call on device pointers; the rows of the attempts behind the first in the slot's scratch, which
+// grows only when a call needs more than any earlier one on the slot.
+int startpath_args(pikamd_solver* s, int slot, int64_t P, int32_t W, int32_t K, const StartPathArrays& d,
+                   uint64_t rng_seed, int64_t problem_offset, pik::StartPathArgs& a) {
+    a = {};
+    a.P = P;
+    a.W = W;
+    a.K = K;
+    a.goal = d.goal;
+    a.seed = d.seed;
+    a.guess = d.guess ? d.guess : d.seed;
+    a.max_step = d.max_step;
+    a.rng_seed = rng_seed;
+    a.problem_offset = problem_offset;
+    a.solution = d.solution;
+    a.status = d.status;
+    a.cost = d.cost;
+    a.stats = d.stats;
+    a.reached = d.reached;
+    a.attempts = d.attempts;
+    a.totals = d.totals;
+    const pik::StartPathScratch l = pik::startpath_scratch(P, W, K, s->chain.dof, d.cost != nullptr, d.stats != nullptr);
+    if (l.total == 0) return 0;
+    pik::DevBuf& buf = ext_of(s)->startpath_rows[slot];
+    if (int rc = buf.ensure(l.total)) return rc;
+    char* w = (char*)buf.p;
+    if (d.stats) a.row_stats = w + l.off_stats;
+    if (d.cost) a.row_cost = (double*)(w + l.off_cost);
+    a.row_solution = (double*)(w + l.off_solution);
+    a.row_status = (int*)(w + l.off_status);
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_search_paths_device(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                   const double* d_goal_pos_quat, const double* d_seed, const double* d_initial_guess,
+                                   const double* d_max_joint_step, uint64_t rng_seed, int64_t problem_offset,
+                                   int32_t max_attempts, double* d_solution, int32_t* d_status, double* d_final_cost,
+                                   pikamd_stats* d_stats, int32_t* d_reached, int32_t* d_attempts,
+                                   pikamd_stats* d_totals, void* stream, int32_t slot) {
+    const StartPathArrays d = {d_goal_pos_quat, d_seed,  d_initial_guess, d_max_joint_step, d_solution, d_status,
+                               d_final_cost,    d_stats, d_reached,       d_attempts,       d_totals};
+    pik::ParamsK pk;
+    if (int rc = check_search_paths(s, p, P, W, max_attempts, d, pk)) return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (P == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    const pik::StartPathOps* ops = startpath_ops_of(s, p);
+    if (!ops) return no_kernels(s->chain.dof);
+    HIP_TRY(hipSetDevice(s->device));
+    pik::StartPathArgs a;
+    if (int rc = startpath_args(s, slot, P, W, max_attempts, d, rng_seed, problem_offset, a)) return rc;
+    return ops->solve(s, pk, a, (hipStream_t)stream, slot);
+}
+
+int32_t pikamd_search_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, const double* goal_pos_quat,
+                            const double* seed, const double* initial_guess, const double* max_joint_step,
+                            uint64_t rng_seed, int64_t problem_offset, int32_t max_attempts, double* solution,
+                            int32_t* status, double* final_cost, pikamd_stats* stats, int32_t* reached,
+                            int32_t* attempts, pikamd_stats* totals) {
+    const StartPathArrays h = {goal_pos_quat, seed,  initial_guess, max_joint_step, solution, status,
+                               final_cost,    stats, reached,       attempts,       totals};
+    pik::ParamsK pk;
+    if (int rc = check_search_paths(s, p, P, W, max_attempts, h, pk)) return rc;
+    if (P == 0) return 0;
+    if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
+    const pik::StartPathOps* ops = startpath_ops_of(s, p);
+    if (!ops) return no_kernels(s->chain.dof);
+    Staging st(s, SEARCH_PATHS.name);
+    if (int rc = st.begin()) return rc;
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
+    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), seed_ = st.in(h.seed, sizeof(double) * d * paths);
+    const int guess = st.in(h.guess, sizeof(double) * d * paths), step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), attempts_ = st.out(h.attempts, sizeof(int32_t) * paths, false);
+    const int totals_ = st.out(h.totals, sizeof(pikamd_stats) * paths, false);
+    if (int rc = st.allocate()) return rc;
+    const StartPathArrays dev = {st.at<const double>(goal), st.at<const double>(seed_), st.at<const double>(guess),
+                                 st.at<const double>(step), st.at<double>(sol),         st.at<int32_t>(status_),
+                                 st.at<double>(cost),       st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_),
+                                 st.at<int32_t>(attempts_), st.at<pikamd_stats>(totals_)};
+    pik::StartPathArgs a;
+    if (int rc = startpath_args(s, Staging::SLOT, P, W, max_attempts, dev, rng_seed, problem_offset, a)) return rc;
+    if (int rc = st.upload()) return rc;
+    return st.finish(ops->solve(s, pk, a, st.stream(), Staging::SLOT));
+}
+
+const char* pikamd_search_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
+    if (!s || !p) return "";
+    const Flavour f = flavour_of(s, p, nullptr);
+    return variant_name(s, f, "startpath", pik::path_lanes(s, P, is_exact(f)));
 }
 
 } // extern "C"

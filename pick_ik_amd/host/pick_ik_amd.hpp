@@ -165,6 +165,14 @@ struct SearchResult {
     std::vector<int32_t> all_status;   // [B][max_attempts], likewise
 };
 
+// Solver::ik_gradient_search_paths: P paths of W waypoints from a pose, the start state restarted until the path holds
+struct SearchPathsResult {
+    PathResult paths;                 // the rows of the kept attempt (the one that held the most waypoints, the first
+                                      // among equals); paths.reached [P]: its leading held waypoints
+    std::vector<int32_t> attempts;    // [P] attempts made
+    std::vector<pikamd_stats> totals; // [P] the counters of every row of every attempt, summed field by field
+};
+
 inline int32_t joint_type_of(const Joint& J) {
     if (J.planar >= 1 && J.planar <= 3) return PIKAMD_JOINT_PLANAR_X + (J.planar - 1);
     if (J.floating >= 1 && J.floating <= 7) return PIKAMD_JOINT_FLOATING_TX + (J.floating - 1);
@@ -488,6 +496,53 @@ class Solver {
                                 max_attempts, r.batch.solution.data(), r.batch.status.data(), r.batch.cost.data(),
                                 r.batch.stats.data(), r.attempts.data(), all_attempts ? r.all_solution.data() : nullptr,
                                 all_attempts ? r.all_status.data() : nullptr) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return r;
+    }
+
+    // Cartesian paths from a pose (pikamd_search_paths): goals [P][W] ([P][W][n_tips] for several tips) row-major,
+    // seeds [P][dof].  Waypoint 0 is solved by ik_gradient from seeds[p] (or initial_guesses[p]) with seeds[p] as the
+    // minimal-displacement reference, the waypoints behind it as ik_gradient_paths does; a path that did not hold
+    // throughout is tried again from a random valid configuration keyed by (rng_seed, problem_offset + p, attempt), up
+    // to max_attempts (1 .. PIKAMD_MAX_ATTEMPTS) times, and the attempt that held the most waypoints is kept.  One
+    // kernel launch for the whole call.
+    SearchPathsResult ik_gradient_search_paths(const std::vector<double>& seeds, const std::vector<Pose>& goals,
+                                               int waypoints, const CostSpec& costs, const GradientIkParams& params,
+                                               int max_attempts, uint64_t rng_seed = 0, int64_t problem_offset = 0,
+                                               bool approx_solution = false,
+                                               const std::vector<double>* max_joint_step = nullptr,
+                                               const std::vector<double>* initial_guesses = nullptr) const {
+        if (waypoints < 1) throw std::invalid_argument("pick_ik_amd: a path has at least one waypoint");
+        if (max_attempts < 1 || max_attempts > PIKAMD_MAX_ATTEMPTS)
+            throw std::invalid_argument("pick_ik_amd: max_attempts outside 1 .. PIKAMD_MAX_ATTEMPTS");
+        const size_t per_path = static_cast<size_t>(waypoints) * static_cast<size_t>(n_tips_);
+        if (goals.size() % per_path != 0) throw std::invalid_argument("pick_ik_amd: goals size is not a multiple of waypoints * n_tips");
+        const size_t P = goals.size() / per_path, rows = P * static_cast<size_t>(waypoints);
+        if (seeds.size() != P * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: seeds size != P * dof");
+        if (initial_guesses && initial_guesses->size() != seeds.size())
+            throw std::invalid_argument("pick_ik_amd: initial_guesses size != P * dof");
+        if (max_joint_step && static_cast<int>(max_joint_step->size()) != dof_)
+            throw std::invalid_argument("pick_ik_amd: max_joint_step size != dof");
+        const pikamd_params p = to_params(costs, nullptr, &params, approx_solution);
+        std::vector<double> g7(7 * goals.size());
+        for (size_t b = 0; b < goals.size(); ++b) {
+            const Pose& g = goals[b];
+            const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+            for (int k = 0; k < 7; ++k) g7[7 * b + k] = v[k];
+        }
+        SearchPathsResult r;
+        r.paths.solution.resize(rows * dof_);
+        r.paths.status.resize(rows);
+        r.paths.cost.resize(rows);
+        r.paths.stats.resize(rows);
+        r.paths.reached.resize(P);
+        r.attempts.resize(P);
+        r.totals.resize(P);
+        if (pikamd_search_paths(h_, &p, static_cast<int64_t>(P), waypoints, g7.data(), seeds.data(),
+                                initial_guesses ? initial_guesses->data() : nullptr,
+                                max_joint_step ? max_joint_step->data() : nullptr, rng_seed, problem_offset, max_attempts,
+                                r.paths.solution.data(), r.paths.status.data(), r.paths.cost.data(), r.paths.stats.data(),
+                                r.paths.reached.data(), r.attempts.data(), r.totals.data()) != 0)
             throw std::runtime_error(pikamd_last_error());
         return r;
     }

@@ -178,6 +178,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_search_batch", "pikamd_search_batch_device", "pikamd_search_kernel_name",
     "pikamd_debug_regime", "pikamd_search_global_batch", "pikamd_search_global_batch_device",
     "pikamd_gate_batch", "pikamd_set_approximate_gate",
+    "pikamd_search_paths", "pikamd_search_paths_device", "pikamd_search_paths_kernel_name",
 )
 
 _libs = {}
@@ -283,6 +284,14 @@ def lib(strict: bool = False):
     L.pikamd_gate_batch.restype = C.c_int32
     L.pikamd_set_approximate_gate.argtypes = [vp, C.POINTER(Gate)]
     L.pikamd_set_approximate_gate.restype = C.c_int32
+    L.pikamd_search_paths.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_uint64, C.c_int64,
+                                      C.c_int32, dp, ip, dp, vp, ip, ip, vp]
+    L.pikamd_search_paths.restype = C.c_int32
+    L.pikamd_search_paths_device.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_uint64,
+                                             C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32]
+    L.pikamd_search_paths_device.restype = C.c_int32
+    L.pikamd_search_paths_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
+    L.pikamd_search_paths_kernel_name.restype = C.c_char_p
     up = C.POINTER(C.c_uint32)
     L.pikamd_debug_regime.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, ip, up, up, ip]
     L.pikamd_debug_regime.restype = C.c_int32
@@ -728,6 +737,75 @@ class Solver:
         """the kernel solve_paths launches for P paths (pikamd_path_kernel_name)"""
         self._env_options()
         return self._L.pikamd_path_kernel_name(self._h, C.byref(params), P).decode()
+
+    # ---- Cartesian paths from a pose: the start state restarted until the path holds -------
+    def search_paths(self, params: Params, goals, seed, max_attempts: int, max_joint_step=None, rng_seed: int = 0,
+                     problem_offset: int = 0, initial_guess=None):
+        """pikamd_search_paths: P paths of W waypoints in local mode (params.mode = 1) from a pose: waypoint 0 is solved
+        from the initial guess with `seed` as the displacement reference, the waypoints behind it as solve_paths does,
+        and a path that did not hold throughout is tried again from a random valid configuration keyed by (rng_seed,
+        problem_offset + p, attempt), up to max_attempts (1..MAX_ATTEMPTS) times; the attempt that held the most
+        waypoints is kept, the first among equals -- one launch.  goals [P][W][7] ([P][W][n_tips][7] for several tips),
+        seed [P][dof], initial_guess [P][dof] or None (= seed), max_joint_step [dof] or None.  Returns (solution
+        [P][W][dof], status [P][W], cost [P][W], stats [P][W], reached [P], attempts [P], totals [P]); the result is
+        what the loop of solve_batch and solve_paths calls in include/pick_ik_amd.h returns, bit for bit."""
+        self._env_options()
+        goals = _f64(goals)
+        tail = (7,) if self.n_tips == 1 else (self.n_tips, 7)
+        if goals.ndim != 2 + len(tail) or goals.shape[2:] != tail:
+            raise ValueError(f"goals: expected [P][W]{list(tail)}, got {list(goals.shape)}")
+        P, W = goals.shape[:2]
+        if W < 1:
+            raise ValueError("goals: a path has at least one waypoint")
+        seed = _f64(seed)
+        if seed.shape != (P, self.dof):
+            raise ValueError(f"seed: expected [{P}][{self.dof}], got {list(seed.shape)}")
+        guess = None
+        if initial_guess is not None:
+            guess = _f64(initial_guess)
+            if guess.shape != (P, self.dof):
+                raise ValueError(f"initial_guess: expected [{P}][{self.dof}], got {list(guess.shape)}")
+        step = None
+        if max_joint_step is not None:
+            step = _f64(max_joint_step)
+            if step.shape != (self.dof,):
+                raise ValueError(f"max_joint_step: expected [{self.dof}], got {list(step.shape)}")
+        K = int(max_attempts)
+        if not 1 <= K <= MAX_ATTEMPTS:
+            raise ValueError(f"max_attempts: expected 1..{MAX_ATTEMPTS}, got {max_attempts}")
+        sol = np.empty((P, W, self.dof))
+        status = np.empty((P, W), dtype=np.int32)
+        cost = np.empty((P, W))
+        stats = np.zeros((P, W), dtype=STATS_DTYPE)
+        reached = np.empty(P, dtype=np.int32)
+        attempts = np.empty(P, dtype=np.int32)
+        totals = np.zeros(P, dtype=STATS_DTYPE)
+        self._chk(self._L.pikamd_search_paths(
+            self._h, C.byref(params), P, W, _dp(goals), _dp(seed), None if guess is None else _dp(guess),
+            None if step is None else _dp(step), C.c_uint64(rng_seed), problem_offset, K, _dp(sol), _ip(status),
+            _dp(cost), stats.ctypes.data_as(C.c_void_p), _ip(reached), _ip(attempts), totals.ctypes.data_as(C.c_void_p)))
+        return sol, status, cost, stats, reached, attempts, totals
+
+    def search_paths_device(self, params: Params, P: int, W: int, d_goals: int, d_seed: int, max_attempts: int,
+                            d_solution: int, d_status: int, d_initial_guess: int = 0, d_max_joint_step: int = 0,
+                            d_cost: int = 0, d_stats: int = 0, d_reached: int = 0, d_attempts: int = 0,
+                            d_totals: int = 0, rng_seed: int = 0, problem_offset: int = 0, stream: int = 0,
+                            slot: int = 0):
+        """Enqueue search_paths on HBM-resident buffers (raw device addresses); returns immediately -- the caller
+        synchronises the stream."""
+        self._env_options()
+        if P < 0 or W < 1:
+            raise ValueError(f"{P} paths of {W} waypoints: expected P >= 0 and W >= 1")
+        self._chk(self._L.pikamd_search_paths_device(
+            self._h, C.byref(params), P, W, d_goals or None, d_seed or None, d_initial_guess or None,
+            d_max_joint_step or None, C.c_uint64(rng_seed), problem_offset, max_attempts, d_solution or None,
+            d_status or None, d_cost or None, d_stats or None, d_reached or None, d_attempts or None, d_totals or None,
+            stream or None, slot))
+
+    def search_paths_kernel_name(self, params: Params, P: int) -> str:
+        """the kernel search_paths launches for P paths (pikamd_search_paths_kernel_name)"""
+        self._env_options()
+        return self._L.pikamd_search_paths_kernel_name(self._h, C.byref(params), P).decode()
 
     # ---- IK with random restarts: local mode (search_batch), the memetic solver (search_global_batch) ----
     def _search(self, entry, params, goal_pos_quat, seed, max_attempts, rng_seed, problem_offset, initial_guess, all_attempts):

@@ -25,7 +25,7 @@ if args and args[0] == "--objs":
     args = args[2:]
 extra = args
 want = set(objs_spec.split(","))
-all_objs = B.library_objects(False)
+all_objs = B.link_objects(False)
 vdir = os.path.join(B.BUILD_DIR, "var_" + name)
 os.makedirs(vdir, exist_ok=True)
 os.makedirs(os.path.join(os.path.dirname(B.LIB), "_variants"), exist_ok=True)
