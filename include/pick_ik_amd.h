@@ -681,8 +681,9 @@ int32_t pikamd_set_approximate_gate(pikamd_solver* s, const pikamd_gate* gate);
  *   NULL), solution [P][W][dof], status [P][W], final_cost [P][W] (may be NULL), stats [P][W] (may be NULL),
  *   reached [P] (may be NULL), attempts [P] (may be NULL), totals [P] (may be NULL).
  * max_attempts is 1..PIKAMD_MAX_ATTEMPTS, W >= 1; P = 0 returns 0.  Not with the option joint_layout = soa.
- * Not served (out of scope): global mode for waypoint 0; a parallel schedule over the attempts (attempt a + 1 depends
- * on how far attempt a got); a relative (mean-step) jump threshold; all_* rows per attempt. */
+ * Not served (out of scope): global mode for waypoint 0 (pikamd_search_global_paths below); a parallel schedule over
+ * the attempts (attempt a + 1 depends on how far attempt a got); a relative (mean-step) jump threshold; all_* rows per
+ * attempt. */
 /* host pointers; synchronous, staged through the library's own pinned buffers and stream like pikamd_solve_batch,
  * behind the same automatic self test of the local-mode kernels */
 int32_t pikamd_search_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
@@ -703,6 +704,73 @@ int32_t pikamd_search_paths_device(pikamd_solver* s, const pikamd_params* p, int
 /* name of the kernel pikamd_search_paths* launches for P paths (see pikamd_kernel_name), e.g.
  * `pik_exact::ik_startpath_team_kernel<7,16>` */
 const char* pikamd_search_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
+/* ---- Cartesian paths from a pose: memetic start, Cartesian path behind -------------------------------
+ * pikamd_search_paths above restarts a LOCAL descent for waypoint 0.  Waypoint 0 is the one waypoint with no
+ * neighbouring joint state -- a cold query from a pose alone, the kind the memetic solver (global mode, the default
+ * mode) exists for.  Here waypoint 0 of every attempt is solved in GLOBAL mode and the waypoints behind it in local
+ * mode, for P paths of W waypoints and up to max_attempts attempts each, in ONE call.  p->mode must be 0 (mode 1 is
+ * refused: pikamd_search_paths serves it).  With p_local = p with mode = 1 the result is DEFINED by the entry points
+ * above, bit for bit:
+ *
+ *   init[p] = initial_guess ? initial_guess[p] : seed[p]
+ *   if init[p] is invalid (a bounded variable outside its limits, or a NaN): init[p] = draw(p, 0, init[p])
+ *   best[p] = -1
+ *   for a in 0 .. max_attempts-1, for every p still open:
+ *     (sol0, st0, c0, stats0) = one pikamd_batch record {B = 1, goal[p][0], seed[p], initial_guess = init[p],
+ *                                problem_offset = problem_offset + p} solved by pikamd_solve_batches with p (global
+ *                                mode) and rng_seed_a = rng_seed + ((uint64_t)a << 32)      (mod 2^64)
+ *     rows_a = W rows:
+ *       row 0 = (sol0, st0, c0, stats0)      (what the call returned: the seed and the guess's cost on failure; NO
+ *                                             joint-step test here)
+ *       if st0 > 0 and W > 1: rows 1.. = pikamd_solve_paths(p_local, P = 1, W - 1, goal[p][1..], start = sol0,
+ *                                                           max_joint_step)
+ *       else:                 rows 1.. = (seed[p], PIKAMD_NOT_ATTEMPTED, 0, zero)
+ *     reached_a = st0 > 0 ? 1 + reached of that path call : 0
+ *     totals[p] += every stats row of rows_a, field by field (wipeouts, pool_erasures and reserved included)
+ *     attempts[p] = a + 1
+ *     if reached_a > best[p]: the outputs of p become rows_a; best[p] = reached_a      (the first among equals wins)
+ *     if reached_a == W: p is closed     else: init[p] = draw(p, a + 1, init[p])
+ *   reached[p] = best[p]
+ *
+ * draw is exactly the draw of pikamd_search_batch: Philox stream RESTART (= 3), keyed by the CALLER's rng_seed (not
+ * rng_seed_a) and problem_offset + p; the attempt seeds rng_seed_a are those of pikamd_search_global_batch.  The
+ * handle's approximate-solution gate is NOT applied, as in pikamd_search_paths.
+ *
+ * Consequences: max_attempts = 1 with a valid initial guess is one global-mode pikamd_solve_batch followed by one
+ * pikamd_solve_paths with p_local.  W = 1 is pikamd_search_global_batch without a gate, with one difference: a problem
+ * that no attempt solved keeps the row of its FIRST attempt (stats[p][0] is the kept attempt's, totals[p] the sum
+ * pikamd_search_global_batch reports).  A call cut into calls or shards with matching problem_offset gives the answers
+ * of one call.  With return_approximate_solution set every waypoint is solved (st > 0), so only a refused jump reopens
+ * a path.
+ *   Arrays and the NULLs allowed: as pikamd_search_paths.
+ * max_attempts is 1..PIKAMD_MAX_ATTEMPTS, W >= 1; P = 0 returns 0.  Not with the option joint_layout = soa.  No
+ * completion counters.  Accepts what pikamd_solve_batch accepts in global mode.
+ * Not served (out of scope): the approximate-solution gate; all_* rows per attempt; a relative (mean-step) jump
+ * threshold; a parallel schedule over the attempts. */
+/* host pointers; synchronous, staged through the library's own pinned buffers and stream, behind the automatic self
+ * tests of BOTH kernel sets (the global-mode one of p, the local-mode one of p_local).  Reads the number of open paths
+ * back behind every attempt and stops enqueuing attempts once it is zero. */
+int32_t pikamd_search_global_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                   const double* goal_pos_quat, const double* seed, const double* initial_guess,
+                                   const double* max_joint_step, uint64_t rng_seed, int64_t problem_offset,
+                                   int32_t max_attempts, double* solution, int32_t* status, double* final_cost,
+                                   pikamd_stats* stats, int32_t* reached, int32_t* attempts, pikamd_stats* totals);
+/* device pointers (max_joint_step too); enqueues ALL max_attempts attempts on `stream` and returns without
+ * synchronising, no self test (see pikamd_solve_batch_device for `slot`): the kernels of an attempt no path is open
+ * for find nothing to do and return.  The scratch of the call (the waypoint-0 goals, the starts, the memetic rows, the
+ * rows of an attempt behind the first, the open list) belongs to the handle's slot; it grows only when a call needs
+ * more than any earlier call on that slot did (a grow frees, and a free synchronises the device: run the largest call
+ * first where that matters). */
+int32_t pikamd_search_global_paths_device(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                          const double* d_goal_pos_quat, const double* d_seed,
+                                          const double* d_initial_guess, const double* d_max_joint_step,
+                                          uint64_t rng_seed, int64_t problem_offset, int32_t max_attempts,
+                                          double* d_solution, int32_t* d_status, double* d_final_cost,
+                                          pikamd_stats* d_stats, int32_t* d_reached, int32_t* d_attempts,
+                                          pikamd_stats* d_totals, void* stream, int32_t slot);
+/* name of the kernel that walks the waypoints behind the first for P paths (see pikamd_kernel_name), e.g.
+ * `pik_exact::ik_globalpath_team_kernel<7,16>`; the memetic kernels in front of it are pikamd_kernel_name's */
+const char* pikamd_search_global_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "pik_globalpath_ops.hpp"
 #include "pik_path_ops.hpp"
 #include "pik_restart_ops.hpp"
 #include "pik_route_ops.hpp"
@@ -47,6 +48,7 @@ PIK_DECLARE_OPS_FAMILY(void, search)
 PIK_DECLARE_OPS_FAMILY(void, route)
 PIK_DECLARE_OPS_FAMILY(void, restart)
 PIK_DECLARE_OPS_FAMILY(void, startpath)
+PIK_DECLARE_OPS_FAMILY(void, globalpath)
 } // namespace pik_exact
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
@@ -82,7 +84,7 @@ enum Flavour {
 #endif
     N_FLAVOURS
 };
-enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, N_FAMILIES };
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -108,6 +110,8 @@ struct SolverExt : pikamd_solver {
     bool gate_params_valid[pik::N_SLOTS] = {};
     // pikamd_search_paths*: per slot the rows of an attempt behind the first (pik_startpath.hpp)
     pik::DevBuf startpath_rows[pik::N_SLOTS];
+    // pikamd_search_global_paths*: per slot the scratch of a call (globalpath_scratch, pik_globalpath_ops.hpp)
+    pik::DevBuf globalpath_rows[pik::N_SLOTS];
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -130,12 +134,13 @@ const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
 #else
      untyped<pik::RouteOps, pik::route_ops>,
 #endif
-     untyped<pik::RestartOps, pik::restart_ops>, untyped<pik::StartPathOps, pik::startpath_ops>},
+     untyped<pik::RestartOps, pik::restart_ops>, untyped<pik::StartPathOps, pik::startpath_ops>,
+     untyped<pik::GlobalPathOps, pik::globalpath_ops>},
 #if !defined(PIK_STRICT)
     {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops,
-     pik_exact::startpath_ops},
-    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr},
-    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr},
+     pik_exact::startpath_ops, pik_exact::globalpath_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr},
 #endif
 };
 // ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
@@ -280,6 +285,10 @@ const pik::SearchOps* search_ops_of(const pikamd_solver* s, const pikamd_params*
 }
 const pik::StartPathOps* startpath_ops_of(const pikamd_solver* s, const pikamd_params* p) {
     return ops_at<pik::StartPathOps>(flavour_of(s, p, nullptr), FAM_STARTPATH, s->chain.dof);
+}
+// (the tail kernels of pikamd_search_global_paths: they walk in local mode, so the flavour is a path call's)
+const pik::GlobalPathOps* globalpath_ops_of(const pikamd_solver* s, const pikamd_params* p) {
+    return ops_at<pik::GlobalPathOps>(flavour_of(s, p, nullptr), FAM_GLOBALPATH, s->chain.dof);
 }
 // ... and the restart launcher of a global-mode call (pik_restart.hpp), in the flavour solve_ops_of picks
 const pik::RestartOps* restart_ops_of(const pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk) {
@@ -507,6 +516,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : ext_of(s)->search_rows) b.release();
     for (auto& b : ext_of(s)->restart_rows) b.release();
     for (auto& b : ext_of(s)->startpath_rows) b.release();
+    for (auto& b : ext_of(s)->globalpath_rows) b.release();
     ext_of(s)->gate_params_dev.release();
     for (auto& j : s->jobs) {
         j.dev.release();
@@ -1423,6 +1433,8 @@ const CallKind SEARCH = {"pikamd_search_batch", 1, "restarts are served in local
                          false, "[B][dof]", "seed"};
 const CallKind SEARCH_PATHS = {"pikamd_search_paths", 1, "paths from a pose are searched in local mode (mode = 1)", "", true,
                                  "[P][W][dof]", "seed"};
+const CallKind SEARCH_GLOBAL_PATHS = {"pikamd_search_global_paths", 0, "the start of a path is searched by the memetic solver (mode = 0)",
+                                      ": local mode is served by pikamd_search_paths", true, "[P][W][dof]", "seed"};
 const CallKind SEARCH_GLOBAL = {"pikamd_search_global_batch", 0, "restarts of the memetic solver (mode = 0)",
                                 ": local mode is served by pikamd_search_batch", false, "[B][dof]", "seed"};
 
@@ -2023,6 +2035,185 @@ int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int
     if (int rc = st.upload()) return rc;
     return st.finish(run_search_global(s, p, pk, ops, restart_args(B, max_attempts, d, rng_seed, problem_offset), d.goal,
                                        d.seed, st.stream(), Staging::SLOT, true));
+}
+
+} // extern "C"
+
+// ---- Cartesian paths from a pose, memetic start (pik_globalpath.hpp) ---------------------------------
+namespace {
+
+// what both entry points refuse: check_call's list for a path call in global mode, then the attempts
+int check_search_global_paths(const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, int32_t K,
+                              const StartPathArrays& d, pik::ParamsK& pk) {
+    if (int rc = check_call(SEARCH_GLOBAL_PATHS, s, p, P, W, d.required_null(), pk)) return rc;
+    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
+        return fail(PIKAMD_EINVAL, "%s: max_attempts %d: expected 1..%d", SEARCH_GLOBAL_PATHS.name, (int)K, PIKAMD_MAX_ATTEMPTS);
+    return 0;
+}
+
+// The attempts of one call on `stream` (device pointers in `d`): per attempt the memetic solve of waypoint 0 for the
+// open paths -- run_solve for attempt 0, the restart launcher behind it, as run_search_global -- and the tail kernel.
+// sync_between: the host-pointer entry point -- the open count is read back behind every tail, and no attempt is
+// enqueued once it is zero.
+int run_search_global_paths(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pik::RestartOps* rops,
+                            const pik::GlobalPathOps* gops, int64_t P, int32_t W, int32_t K, const StartPathArrays& d,
+                            uint64_t rng_seed, int64_t problem_offset, hipStream_t stream, int slot, bool sync_between) {
+    const int g7 = 7 * s->n_tips;
+    const pik::GlobalPathScratch l =
+        pik::globalpath_scratch(P, W, K, s->chain.dof, g7, d.cost != nullptr, d.stats != nullptr);
+    pik::DevBuf& buf = ext_of(s)->globalpath_rows[slot];
+    if (int rc = buf.ensure(l.total)) return rc;
+    if (int rc = rops->reserve(s, p, pk, P, slot)) return rc;
+    char* w = (char*)buf.p;
+    unsigned* n_list = (unsigned*)(s->counters + pik::COUNTER_BLOCK * (size_t)slot + 128);
+    pik::GlobalPathArgs a = {};
+    a.P = P;
+    a.W = W;
+    a.K = K;
+    a.g7 = g7;
+    a.goal = d.goal;
+    a.seed = d.seed;
+    a.user_guess = d.guess ? d.guess : d.seed;
+    a.max_step = d.max_step;
+    a.rng_seed = rng_seed;
+    a.problem_offset = problem_offset;
+    a.solution = d.solution;
+    a.status = d.status;
+    a.cost = d.cost;
+    a.stats = d.stats;
+    a.reached = d.reached;
+    a.attempts = d.attempts;
+    a.totals = d.totals;
+    if (K > 1) {
+        if (d.stats) a.row_stats = w + l.off_row_stats;
+        if (d.cost) a.row_cost = (double*)(w + l.off_row_cost);
+        a.row_solution = (double*)(w + l.off_row_solution);
+        a.row_status = (int*)(w + l.off_row_status);
+    }
+    a.goal0 = (double*)(w + l.off_goal0);
+    a.guess = (double*)(w + l.off_guess);
+    a.m_solution = (const double*)(w + l.off_m_solution);
+    a.m_cost = (const double*)(w + l.off_m_cost);
+    a.m_stats = w + l.off_m_stats;
+    a.m_status = (const int*)(w + l.off_m_status);
+    a.best = (int*)(w + l.off_best);
+    a.open = (int*)(w + l.off_open);
+    a.list = (int*)(w + l.off_list);
+    a.n_list = n_list;
+    pik::BatchRecord rec;
+    std::memset(&rec, 0, sizeof rec);
+    rec.B = P;
+    rec.goal = a.goal0;
+    rec.seed = d.seed;
+    rec.guess = a.guess;
+    rec.problem_offset = problem_offset;
+    rec.solution = (double*)(w + l.off_m_solution);
+    rec.status = (int*)(w + l.off_m_status);
+    rec.cost = (double*)(w + l.off_m_cost);
+    rec.stats = w + l.off_m_stats;
+    // (a launch that failed half-way leaves counters behind: the next call on the slot clears them)
+    auto give_up = [&](int rc) {
+        s->counters_dirty[slot] = true;
+        return rc;
+    };
+    if (s->counters_dirty[slot]) {
+        HIP_TRY(hipMemsetAsync(s->counters + pik::COUNTER_BLOCK * (size_t)slot, 0, pik::COUNTER_BLOCK, stream));
+        s->counters_dirty[slot] = false;
+    }
+    if (int rc = gops->prepare(s, pk, a, stream, slot)) return rc;
+    long long open = P;
+    for (int at = 0; at < K; ++at) {
+        const unsigned long long seed_a = pik::restart_attempt_seed(rng_seed, at);
+        if (at == 0) {
+            if (int rc = run_solve(s, p, pk, &rec, 1, seed_a, stream, slot)) return give_up(rc);
+        } else {
+            pik::BatchRecord copy = rec; // (the launch fills in `start`)
+            if (int rc = rops->attempt(s, p, pk, &copy, seed_a, a.list, sync_between ? open : -1, stream, slot))
+                return give_up(rc);
+        }
+        a.attempt = at;
+        a.last = (at == K - 1) ? 1 : 0;
+        if (int rc = gops->tail(s, pk, a, stream, slot)) return give_up(rc);
+        if (sync_between && !a.last) {
+            unsigned cnt = 0;
+            hipError_t e = hipMemcpyAsync(&cnt, n_list, sizeof cnt, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return give_up(fail(PIKAMD_EHIP, "%s: %s", SEARCH_GLOBAL_PATHS.name, hipGetErrorString(e)));
+            open = (long long)cnt;
+            if (open == 0) break;
+        }
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_search_global_paths_device(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                          const double* d_goal_pos_quat, const double* d_seed,
+                                          const double* d_initial_guess, const double* d_max_joint_step,
+                                          uint64_t rng_seed, int64_t problem_offset, int32_t max_attempts,
+                                          double* d_solution, int32_t* d_status, double* d_final_cost,
+                                          pikamd_stats* d_stats, int32_t* d_reached, int32_t* d_attempts,
+                                          pikamd_stats* d_totals, void* stream, int32_t slot) {
+    const StartPathArrays d = {d_goal_pos_quat, d_seed,  d_initial_guess, d_max_joint_step, d_solution, d_status,
+                               d_final_cost,    d_stats, d_reached,       d_attempts,       d_totals};
+    pik::ParamsK pk;
+    if (int rc = check_search_global_paths(s, p, P, W, max_attempts, d, pk)) return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (P == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    const pik::RestartOps* rops = restart_ops_of(s, p, pk);
+    const pik::GlobalPathOps* gops = globalpath_ops_of(s, p);
+    if (!rops || !gops) return no_kernels(s->chain.dof);
+    HIP_TRY(hipSetDevice(s->device));
+    return run_search_global_paths(s, p, pk, rops, gops, P, W, max_attempts, d, rng_seed, problem_offset,
+                                   (hipStream_t)stream, slot, false);
+}
+
+int32_t pikamd_search_global_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W,
+                                   const double* goal_pos_quat, const double* seed, const double* initial_guess,
+                                   const double* max_joint_step, uint64_t rng_seed, int64_t problem_offset,
+                                   int32_t max_attempts, double* solution, int32_t* status, double* final_cost,
+                                   pikamd_stats* stats, int32_t* reached, int32_t* attempts, pikamd_stats* totals) {
+    const StartPathArrays h = {goal_pos_quat, seed,  initial_guess, max_joint_step, solution, status,
+                               final_cost,    stats, reached,       attempts,       totals};
+    pik::ParamsK pk;
+    if (int rc = check_search_global_paths(s, p, P, W, max_attempts, h, pk)) return rc;
+    if (P == 0) return 0;
+    // (both kernel sets: the GLOBAL-mode one of waypoint 0 and the local-mode one of the waypoints behind it)
+    if (int rc = maybe_self_test(s, p)) return rc;
+    pikamd_params p_local = *p;
+    p_local.mode = 1;
+    if (int rc = maybe_self_test(s, &p_local)) return rc;
+    const pik::RestartOps* rops = restart_ops_of(s, p, pk);
+    const pik::GlobalPathOps* gops = globalpath_ops_of(s, p);
+    if (!rops || !gops) return no_kernels(s->chain.dof);
+    Staging st(s, SEARCH_GLOBAL_PATHS.name);
+    if (int rc = st.begin()) return rc;
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
+    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), seed_ = st.in(h.seed, sizeof(double) * d * paths);
+    const int guess = st.in(h.guess, sizeof(double) * d * paths), step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), attempts_ = st.out(h.attempts, sizeof(int32_t) * paths, false);
+    const int totals_ = st.out(h.totals, sizeof(pikamd_stats) * paths, false);
+    if (int rc = st.allocate()) return rc;
+    const StartPathArrays dev = {st.at<const double>(goal), st.at<const double>(seed_), st.at<const double>(guess),
+                                 st.at<const double>(step), st.at<double>(sol),         st.at<int32_t>(status_),
+                                 st.at<double>(cost),       st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_),
+                                 st.at<int32_t>(attempts_), st.at<pikamd_stats>(totals_)};
+    if (int rc = st.upload()) return rc;
+    return st.finish(run_search_global_paths(s, p, pk, rops, gops, P, W, max_attempts, dev, rng_seed, problem_offset,
+                                             st.stream(), Staging::SLOT, true));
+}
+
+const char* pikamd_search_global_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
+    if (!s || !p) return "";
+    const Flavour f = flavour_of(s, p, nullptr);
+    return variant_name(s, f, "globalpath", pik::path_lanes(s, P, is_exact(f)));
 }
 
 } // extern "C"

@@ -166,6 +166,7 @@ struct SearchResult {
 };
 
 // Solver::ik_gradient_search_paths: P paths of W waypoints from a pose, the start state restarted until the path holds
+// (ik_memetic_search_paths: waypoint 0 by the memetic solver)
 struct SearchPathsResult {
     PathResult paths;                 // the rows of the kept attempt (the one that held the most waypoints, the first
                                       // among equals); paths.reached [P]: its leading held waypoints
@@ -586,6 +587,54 @@ class Solver {
                                        r.batch.cost.data(), r.batch.stats.data(), r.attempts.data(),
                                        all_attempts ? r.all_solution.data() : nullptr,
                                        all_attempts ? r.all_status.data() : nullptr) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return r;
+    }
+
+    // Cartesian paths from a pose with a memetic start (pikamd_search_global_paths): as ik_gradient_search_paths, but
+    // waypoint 0 of every attempt is solved by ik_memetic (attempt a with rng_seed + (a << 32), as
+    // ik_memetic_search_batch) and the waypoints behind it by ik_gradient with the step size and cost delta of
+    // params.gd_params and at most path_max_iterations steps each (0: the default of pikamd_default_params).
+    SearchPathsResult ik_memetic_search_paths(const std::vector<double>& seeds, const std::vector<Pose>& goals,
+                                              int waypoints, const CostSpec& costs, const MemeticIkParams& params,
+                                              int max_attempts, uint64_t rng_seed = 0, int64_t problem_offset = 0,
+                                              bool approx_solution = false,
+                                              const std::vector<double>* max_joint_step = nullptr,
+                                              const std::vector<double>* initial_guesses = nullptr,
+                                              int path_max_iterations = 0) const {
+        if (waypoints < 1) throw std::invalid_argument("pick_ik_amd: a path has at least one waypoint");
+        if (max_attempts < 1 || max_attempts > PIKAMD_MAX_ATTEMPTS)
+            throw std::invalid_argument("pick_ik_amd: max_attempts outside 1 .. PIKAMD_MAX_ATTEMPTS");
+        const size_t per_path = static_cast<size_t>(waypoints) * static_cast<size_t>(n_tips_);
+        if (goals.size() % per_path != 0) throw std::invalid_argument("pick_ik_amd: goals size is not a multiple of waypoints * n_tips");
+        const size_t P = goals.size() / per_path, rows = P * static_cast<size_t>(waypoints);
+        if (seeds.size() != P * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: seeds size != P * dof");
+        if (initial_guesses && initial_guesses->size() != seeds.size())
+            throw std::invalid_argument("pick_ik_amd: initial_guesses size != P * dof");
+        if (max_joint_step && static_cast<int>(max_joint_step->size()) != dof_)
+            throw std::invalid_argument("pick_ik_amd: max_joint_step size != dof");
+        pikamd_params p = to_params(costs, &params, nullptr, approx_solution);
+        if (path_max_iterations > 0) p.gd_max_iters = path_max_iterations;
+        std::vector<double> g7(7 * goals.size());
+        for (size_t b = 0; b < goals.size(); ++b) {
+            const Pose& g = goals[b];
+            const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+            for (int k = 0; k < 7; ++k) g7[7 * b + k] = v[k];
+        }
+        SearchPathsResult r;
+        r.paths.solution.resize(rows * dof_);
+        r.paths.status.resize(rows);
+        r.paths.cost.resize(rows);
+        r.paths.stats.resize(rows);
+        r.paths.reached.resize(P);
+        r.attempts.resize(P);
+        r.totals.resize(P);
+        if (pikamd_search_global_paths(h_, &p, static_cast<int64_t>(P), waypoints, g7.data(), seeds.data(),
+                                       initial_guesses ? initial_guesses->data() : nullptr,
+                                       max_joint_step ? max_joint_step->data() : nullptr, rng_seed, problem_offset,
+                                       max_attempts, r.paths.solution.data(), r.paths.status.data(), r.paths.cost.data(),
+                                       r.paths.stats.data(), r.paths.reached.data(), r.attempts.data(),
+                                       r.totals.data()) != 0)
             throw std::runtime_error(pikamd_last_error());
         return r;
     }

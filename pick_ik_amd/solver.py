@@ -179,6 +179,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_debug_regime", "pikamd_search_global_batch", "pikamd_search_global_batch_device",
     "pikamd_gate_batch", "pikamd_set_approximate_gate",
     "pikamd_search_paths", "pikamd_search_paths_device", "pikamd_search_paths_kernel_name",
+    "pikamd_search_global_paths", "pikamd_search_global_paths_device", "pikamd_search_global_paths_kernel_name",
 )
 
 _libs = {}
@@ -292,6 +293,12 @@ def lib(strict: bool = False):
     L.pikamd_search_paths_device.restype = C.c_int32
     L.pikamd_search_paths_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
     L.pikamd_search_paths_kernel_name.restype = C.c_char_p
+    L.pikamd_search_global_paths.argtypes = L.pikamd_search_paths.argtypes
+    L.pikamd_search_global_paths.restype = C.c_int32
+    L.pikamd_search_global_paths_device.argtypes = L.pikamd_search_paths_device.argtypes
+    L.pikamd_search_global_paths_device.restype = C.c_int32
+    L.pikamd_search_global_paths_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
+    L.pikamd_search_global_paths_kernel_name.restype = C.c_char_p
     up = C.POINTER(C.c_uint32)
     L.pikamd_debug_regime.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, ip, up, up, ip]
     L.pikamd_debug_regime.restype = C.c_int32
@@ -749,6 +756,12 @@ class Solver:
         seed [P][dof], initial_guess [P][dof] or None (= seed), max_joint_step [dof] or None.  Returns (solution
         [P][W][dof], status [P][W], cost [P][W], stats [P][W], reached [P], attempts [P], totals [P]); the result is
         what the loop of solve_batch and solve_paths calls in include/pick_ik_amd.h returns, bit for bit."""
+        return self._search_paths("pikamd_search_paths", params, goals, seed, max_attempts, max_joint_step, rng_seed,
+                                  problem_offset, initial_guess)
+
+    def _search_paths(self, entry, params, goals, seed, max_attempts, max_joint_step, rng_seed, problem_offset,
+                      initial_guess):
+        """search_paths / search_global_paths; entry: the name of the library's entry point"""
         self._env_options()
         goals = _f64(goals)
         tail = (7,) if self.n_tips == 1 else (self.n_tips, 7)
@@ -780,7 +793,7 @@ class Solver:
         reached = np.empty(P, dtype=np.int32)
         attempts = np.empty(P, dtype=np.int32)
         totals = np.zeros(P, dtype=STATS_DTYPE)
-        self._chk(self._L.pikamd_search_paths(
+        self._chk(getattr(self._L, entry)(
             self._h, C.byref(params), P, W, _dp(goals), _dp(seed), None if guess is None else _dp(guess),
             None if step is None else _dp(step), C.c_uint64(rng_seed), problem_offset, K, _dp(sol), _ip(status),
             _dp(cost), stats.ctypes.data_as(C.c_void_p), _ip(reached), _ip(attempts), totals.ctypes.data_as(C.c_void_p)))
@@ -793,10 +806,18 @@ class Solver:
                             slot: int = 0):
         """Enqueue search_paths on HBM-resident buffers (raw device addresses); returns immediately -- the caller
         synchronises the stream."""
+        self._search_paths_device("pikamd_search_paths_device", params, P, W, d_goals, d_seed, max_attempts, d_solution,
+                                  d_status, d_initial_guess, d_max_joint_step, d_cost, d_stats, d_reached, d_attempts,
+                                  d_totals, rng_seed, problem_offset, stream, slot)
+
+    def _search_paths_device(self, entry, params, P, W, d_goals, d_seed, max_attempts, d_solution, d_status,
+                             d_initial_guess, d_max_joint_step, d_cost, d_stats, d_reached, d_attempts, d_totals,
+                             rng_seed, problem_offset, stream, slot):
+        """search_paths_device / search_global_paths_device; entry: the name of the library's entry point"""
         self._env_options()
         if P < 0 or W < 1:
             raise ValueError(f"{P} paths of {W} waypoints: expected P >= 0 and W >= 1")
-        self._chk(self._L.pikamd_search_paths_device(
+        self._chk(getattr(self._L, entry)(
             self._h, C.byref(params), P, W, d_goals or None, d_seed or None, d_initial_guess or None,
             d_max_joint_step or None, C.c_uint64(rng_seed), problem_offset, max_attempts, d_solution or None,
             d_status or None, d_cost or None, d_stats or None, d_reached or None, d_attempts or None, d_totals or None,
@@ -806,6 +827,32 @@ class Solver:
         """the kernel search_paths launches for P paths (pikamd_search_paths_kernel_name)"""
         self._env_options()
         return self._L.pikamd_search_paths_kernel_name(self._h, C.byref(params), P).decode()
+
+    # ---- Cartesian paths from a pose, memetic start: waypoint 0 by the memetic solver, the path behind it ----
+    def search_global_paths(self, params: Params, goals, seed, max_attempts: int, max_joint_step=None,
+                            rng_seed: int = 0, problem_offset: int = 0, initial_guess=None):
+        """pikamd_search_global_paths: search_paths with waypoint 0 of every attempt solved by the memetic solver
+        (params.mode = 0; attempt a with rng_seed + (a << 32), as search_global_batch) and the waypoints behind it in
+        local mode, as solve_paths does with mode = 1.  Arguments and returns as search_paths; the result is what the
+        loop of solve_batches and solve_paths calls in include/pick_ik_amd.h returns, bit for bit."""
+        return self._search_paths("pikamd_search_global_paths", params, goals, seed, max_attempts, max_joint_step,
+                                  rng_seed, problem_offset, initial_guess)
+
+    def search_global_paths_device(self, params: Params, P: int, W: int, d_goals: int, d_seed: int, max_attempts: int,
+                                   d_solution: int, d_status: int, d_initial_guess: int = 0,
+                                   d_max_joint_step: int = 0, d_cost: int = 0, d_stats: int = 0, d_reached: int = 0,
+                                   d_attempts: int = 0, d_totals: int = 0, rng_seed: int = 0, problem_offset: int = 0,
+                                   stream: int = 0, slot: int = 0):
+        """Enqueue search_global_paths on HBM-resident buffers (raw device addresses): every attempt is enqueued,
+        nothing synchronises -- the caller synchronises the stream."""
+        self._search_paths_device("pikamd_search_global_paths_device", params, P, W, d_goals, d_seed, max_attempts,
+                                  d_solution, d_status, d_initial_guess, d_max_joint_step, d_cost, d_stats, d_reached,
+                                  d_attempts, d_totals, rng_seed, problem_offset, stream, slot)
+
+    def search_global_paths_kernel_name(self, params: Params, P: int) -> str:
+        """the kernel that walks the waypoints behind the first for P paths (pikamd_search_global_paths_kernel_name)"""
+        self._env_options()
+        return self._L.pikamd_search_global_paths_kernel_name(self._h, C.byref(params), P).decode()
 
     # ---- IK with random restarts: local mode (search_batch), the memetic solver (search_global_batch) ----
     def _search(self, entry, params, goal_pos_quat, seed, max_attempts, rng_seed, problem_offset, initial_guess, all_attempts):
