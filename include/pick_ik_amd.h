@@ -771,6 +771,98 @@ int32_t pikamd_search_global_paths_device(pikamd_solver* s, const pikamd_params*
 /* name of the kernel that walks the waypoints behind the first for P paths (see pikamd_kernel_name), e.g.
  * `pik_exact::ik_globalpath_team_kernel<7,16>`; the memetic kernels in front of it are pikamd_kernel_name's */
 const char* pikamd_search_global_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
+/* ---- computeCartesianPath in one call -----------------------------------------------------------------
+ * pikamd_solve_paths walks waypoints the caller made.  What computeCartesianPath is GIVEN is a start joint state, a
+ * target pose or offset, a maximum end-effector step and jump thresholds; here P such motions go in, the poses are
+ * generated on the device, every path is walked for its OWN number of steps, the absolute and the relative jump test
+ * are applied and MoveIt's fraction comes out.
+ *
+ * pikamd_interpolate_poses (a host function: no handle, no device, like pikamd_shard_bounds).  Quaternions are w x y z.
+ * Per path, a = the start pose (ta, qa) and b the resolved target:
+ *   GLOBAL: (tt, qt)        TIP: (ta + R(qa) tt, qa (x) qt)        OFFSET: (ta + tt, qa)
+ * (R(q): Eigen's toRotationMatrix, no normalisation; (x): the Hamilton product).
+ *   trans = |tb - ta|;  rot = 2 atan2(|d.xyz|, |d.w|), d = qa (x) conj(qb)           (Eigen's angularDistance)
+ *   t_steps = max_translation > 0 ? floor(trans / max_translation) : 0;  r_steps likewise from rot and max_rotation
+ *   n = max(t_steps, r_steps) + 1, raised to the minimum min_steps gives (0: 10 when jump_factor > 0, else 1);
+ *   a quotient that is not finite or not below 2^31 gives n = INT32_MAX;  steps[p] = n
+ *   waypoint k (0 <= k < n): pct = (double)(k + 1) / (double)n; position pct tb + (1 - pct) ta; orientation Eigen's
+ *   slerp(pct, qa, qb): d = qa . qb; |d| >= 1 - 2^-52: the scales are 1 - pct and pct, else theta = acos|d| and they
+ *   are sin((1 - pct) theta) / sin theta and sin(pct theta) / sin theta; the second is negated when d < 0; the result
+ *   is not normalised.
+ * Rows k >= n, and EVERY row of a path with n > W, hold b.  start_pose [P][7], target [P][7], goals [P][W][7],
+ * steps [P].  Refused (PIKAMD_EINVAL): a NULL pointer, frame outside 0..2, W < 1, min_steps < 0, neither
+ * max_translation nor max_rotation > 0.  P = 0 returns 0.
+ * The arithmetic is one header (pik_interp.hpp: IEEE operations rounded one by one, IEEE square roots and quotients,
+ * sine and arctangent of one fixed form) compiled for the host and for the device: within one library the host
+ * function and the kernels return the SAME BITS in every flavour.
+ *
+ * pikamd_cartesian_paths.  p->mode must be 1.  The result is DEFINED by the entry points above, bit for bit:
+ *
+ *   pose0 = pikamd_fk_batch(s, P, start)
+ *   (goals, steps) = pikamd_interpolate_poses(c, P, W, pose0, target)
+ *   for every p, n = steps[p]:
+ *     if n > W:  every row = (start[p], PIKAMD_NOT_ATTEMPTED, 0, zero); reached[p] = 0; fraction[p] = 0
+ *     else:
+ *       rows 0..n-1 = pikamd_solve_paths(p, P = 1, W = n, goals[p][0..n-1], start[p], max_joint_step); r = its reached
+ *       rows n..W-1 = (solution row n-1, PIKAMD_NOT_ATTEMPTED, 0, zero)
+ *       fraction[p] = (double)r / (double)n
+ *       if c->jump_factor > 0 and r >= 1:
+ *         traj[0] = start[p]; traj[i] = solution[p][i-1] for i = 1..r
+ *         dist[i] = sum over j ascending of fabs(traj[i+1][j] - traj[i][j]), i = 0..r-1   (from 0.0, every operation
+ *                   rounded on its own)
+ *         total = sum of dist[i], i ascending;  thres = c->jump_factor * (total / (double)r)
+ *         for the first i with dist[i] > thres:
+ *           fraction[p] *= (double)(i+1) / (double)(r+1)                          (MoveIt: (i+1) / traj.size())
+ *           solution rows i..W-1 = traj[i]; status[p][i] = PIKAMD_PATH_RELATIVE_JUMP (its cost and stats stay what the
+ *           solve returned); rows i+1..W-1 = (traj[i], PIKAMD_NOT_ATTEMPTED, 0, zero);  r = i
+ *       reached[p] = r
+ *
+ * Consequences: when jump_factor is not > 0 and every steps[p] equals W, the call is pikamd_fk_batch +
+ * pikamd_interpolate_poses + pikamd_solve_paths.  A path with steps[p] > W was not walked: call again with W >= the
+ * largest steps[p].  dist is MoveIt's group distance for bounded revolute and prismatic variables; continuous, planar
+ * and floating variables are compared unwrapped, variable by variable -- the departure max_joint_step already has.
+ * The absolute thresholds (JumpThreshold::revolute and prismatic) are the caller's max_joint_step.  The handle's
+ * approximate-solution gate is NOT applied, as in pikamd_solve_paths.
+ *   start [P][dof], target [P][7], max_joint_step [dof] (may be NULL), solution [P][W][dof], status [P][W],
+ *   final_cost [P][W] (may be NULL), stats [P][W] (may be NULL), reached [P] (may be NULL), steps [P] (REQUIRED),
+ *   fraction [P] (may be NULL), goals [P][W][7] (may be NULL): the poses that were walked.
+ * Refused: several tip frames (PIKAMD_EUNSUPPORTED); mode 0, joint_layout = soa, steps == NULL and everything
+ * pikamd_interpolate_poses refuses (PIKAMD_EINVAL).  P = 0 returns 0.
+ * Not served (out of scope): the relative test inside pikamd_search_paths and pikamd_search_global_paths, a validity
+ * callback, sharding, a plugin-shim entry (KinematicsBase has none).
+ * pikamd_cartesian_paths: host pointers; synchronous, staged through the library's own pinned buffers and stream like
+ * pikamd_solve_paths, behind the same automatic self test of the local-mode kernels; honours lanes_per_elite as
+ * pikamd_solve_paths does.  pikamd_cartesian_paths_device: device pointers (max_joint_step too); enqueues a prepare
+ * kernel (forward kinematics, poses, steps) and the walk on `stream` and returns without synchronising, no self test
+ * (see pikamd_solve_batch_device for `slot`).  Without d_goals the poses are kept in scratch that belongs to the
+ * handle's slot; it grows only when a call needs more than any earlier call on that slot did (a grow frees, and a free
+ * synchronises the device: run the largest call first where that matters).  pikamd_cartesian_kernel_name: the kernel
+ * that walks P paths (see pikamd_kernel_name), e.g. `pik_exact::ik_cartesian_team_kernel<7,16>`. */
+#define PIKAMD_PATH_RELATIVE_JUMP (-1003) /* outside MoveItErrorCodes, like PIKAMD_PATH_JUMP */
+#define PIKAMD_CARTESIAN_GLOBAL 0 /* target is a pose in the base frame */
+#define PIKAMD_CARTESIAN_TIP 1    /* target is relative to the start tip frame: b = a * target */
+#define PIKAMD_CARTESIAN_OFFSET 2 /* target's translation is added to the start's in the base frame, orientation kept
+                                     (target's quaternion ignored) */
+typedef struct pikamd_cartesian {
+    int32_t frame;          /* PIKAMD_CARTESIAN_* */
+    int32_t min_steps;      /* 0 = MoveIt's rule: 10 when jump_factor > 0, else 1; > 0: that many */
+    double max_translation; /* MaxEEFStep::translation; not > 0: not limiting */
+    double max_rotation;    /* MaxEEFStep::rotation (rad); not > 0: not limiting */
+    double jump_factor;     /* relative jump threshold factor; not > 0: no relative test */
+} pikamd_cartesian;
+int32_t pikamd_interpolate_poses(const pikamd_cartesian* c, int64_t P, int32_t W, const double* start_pose,
+                                 const double* target, double* goals, int32_t* steps);
+int32_t pikamd_cartesian_paths(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                               int32_t W, const double* start, const double* target, const double* max_joint_step,
+                               double* solution, int32_t* status, double* final_cost, pikamd_stats* stats,
+                               int32_t* reached, int32_t* steps, double* fraction, double* goals);
+int32_t pikamd_cartesian_paths_device(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                                      int32_t W, const double* d_start, const double* d_target,
+                                      const double* d_max_joint_step, double* d_solution, int32_t* d_status,
+                                      double* d_final_cost, pikamd_stats* d_stats, int32_t* d_reached,
+                                      int32_t* d_steps, double* d_fraction, double* d_goals, void* stream,
+                                      int32_t slot);
+const char* pikamd_cartesian_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -5,5 +5,6 @@ include/pick_ik_amd.h), ``solver.py`` (ctypes mirror of the reference's solver i
 ``robots.py`` (serial-chain tables) and ``build.py``.
 """
 from . import robots  # noqa: F401
-from .solver import (APPROXIMATE, GATE_REFUSED, MAX_ATTEMPTS, NO_IK_SOLUTION, NOT_ATTEMPTED, PATH_JUMP, SUCCESS,  # noqa: F401
-                     Gate, Params, PickIkAmdError, Solver, default_params, ik_gradient, ik_memetic)
+from .solver import (APPROXIMATE, CARTESIAN_GLOBAL, CARTESIAN_OFFSET, CARTESIAN_TIP, GATE_REFUSED, MAX_ATTEMPTS,  # noqa: F401
+                     NO_IK_SOLUTION, NOT_ATTEMPTED, PATH_JUMP, PATH_RELATIVE_JUMP, SUCCESS, Cartesian, Gate, Params,
+                     PickIkAmdError, Solver, default_params, ik_gradient, ik_memetic, interpolate_poses)

@@ -16,7 +16,9 @@
 #include <thread>
 #include <vector>
 
+#include "pik_cartesian_ops.hpp"
 #include "pik_globalpath_ops.hpp"
+#include "pik_interp.hpp"
 #include "pik_path_ops.hpp"
 #include "pik_restart_ops.hpp"
 #include "pik_route_ops.hpp"
@@ -49,6 +51,7 @@ PIK_DECLARE_OPS_FAMILY(void, route)
 PIK_DECLARE_OPS_FAMILY(void, restart)
 PIK_DECLARE_OPS_FAMILY(void, startpath)
 PIK_DECLARE_OPS_FAMILY(void, globalpath)
+PIK_DECLARE_OPS_FAMILY(void, cartesian)
 } // namespace pik_exact
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
@@ -84,7 +87,7 @@ enum Flavour {
 #endif
     N_FLAVOURS
 };
-enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, N_FAMILIES };
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -112,6 +115,8 @@ struct SolverExt : pikamd_solver {
     pik::DevBuf startpath_rows[pik::N_SLOTS];
     // pikamd_search_global_paths*: per slot the scratch of a call (globalpath_scratch, pik_globalpath_ops.hpp)
     pik::DevBuf globalpath_rows[pik::N_SLOTS];
+    // pikamd_cartesian_paths_device: per slot the interpolated poses of a call whose caller keeps none
+    pik::DevBuf cartesian_goals[pik::N_SLOTS];
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -135,12 +140,12 @@ const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
      untyped<pik::RouteOps, pik::route_ops>,
 #endif
      untyped<pik::RestartOps, pik::restart_ops>, untyped<pik::StartPathOps, pik::startpath_ops>,
-     untyped<pik::GlobalPathOps, pik::globalpath_ops>},
+     untyped<pik::GlobalPathOps, pik::globalpath_ops>, untyped<pik::CartesianOps, pik::cartesian_ops>},
 #if !defined(PIK_STRICT)
     {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops,
-     pik_exact::startpath_ops, pik_exact::globalpath_ops},
-    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr},
-    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr},
+     pik_exact::startpath_ops, pik_exact::globalpath_ops, pik_exact::cartesian_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr},
 #endif
 };
 // ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
@@ -516,6 +521,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : ext_of(s)->search_rows) b.release();
     for (auto& b : ext_of(s)->restart_rows) b.release();
     for (auto& b : ext_of(s)->startpath_rows) b.release();
+    for (auto& b : ext_of(s)->cartesian_goals) b.release();
     for (auto& b : ext_of(s)->globalpath_rows) b.release();
     ext_of(s)->gate_params_dev.release();
     for (auto& j : s->jobs) {
@@ -2214,6 +2220,169 @@ const char* pikamd_search_global_paths_kernel_name(const pikamd_solver* s, const
     if (!s || !p) return "";
     const Flavour f = flavour_of(s, p, nullptr);
     return variant_name(s, f, "globalpath", pik::path_lanes(s, P, is_exact(f)));
+}
+
+} // extern "C"
+
+// ---- computeCartesianPath in one call (pik_cartesian.hpp, pik_interp.hpp) ---------------------------
+namespace {
+
+const CallKind CARTESIAN = {"pikamd_cartesian_paths", 1, "Cartesian motions are walked in local mode (mode = 1)", "", true,
+                            "[P][W][dof]", "start"};
+
+// what pikamd_interpolate_poses refuses of its parameter object (W apart)
+int check_cartesian(const char* who, const pikamd_cartesian* c) {
+    if (!c) return fail(PIKAMD_EINVAL, "%s: the pikamd_cartesian is NULL", who);
+    if (c->frame < PIKAMD_CARTESIAN_GLOBAL || c->frame > PIKAMD_CARTESIAN_OFFSET)
+        return fail(PIKAMD_EINVAL, "%s: frame %d: expected 0 (global), 1 (tip) or 2 (offset)", who, (int)c->frame);
+    if (c->min_steps < 0) return fail(PIKAMD_EINVAL, "%s: min_steps %d: expected >= 0", who, (int)c->min_steps);
+    if (!(c->max_translation > 0.0) && !(c->max_rotation > 0.0))
+        return fail(PIKAMD_EINVAL, "%s: neither max_translation nor max_rotation is > 0: no step size", who);
+    return 0;
+}
+
+pik_interp::Motion motion_of(const pikamd_cartesian* c) {
+    return {(int)c->frame, pik::cartesian_min_steps(c->min_steps, c->jump_factor), c->max_translation, c->max_rotation};
+}
+
+// the arrays of a pikamd_cartesian_paths call: host pointers, or device pointers
+struct CartesianArrays {
+    const double *start, *target, *max_step;
+    double* solution;
+    int32_t* status;
+    double* cost;
+    pikamd_stats* stats;
+    int32_t *reached, *steps;
+    double *fraction, *goals;
+};
+
+// what both entry points refuse: check_call's list for a path call, the parameter object, several tip frames
+int check_cartesian_paths(const pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P, int32_t W,
+                          const CartesianArrays& d, pik::ParamsK& pk) {
+    if (int rc = check_call(CARTESIAN, s, p, P, W, false, pk)) return rc;
+    if (int rc = check_cartesian(CARTESIAN.name, c)) return rc;
+    if (s->n_tips > 1)
+        return fail(PIKAMD_EUNSUPPORTED, "%s: %d tip frames: a Cartesian motion is that of one tip frame", CARTESIAN.name, s->n_tips);
+    if (!d.steps) return fail(PIKAMD_EINVAL, "%s: steps must not be NULL (a path with steps[p] > W was not walked)", CARTESIAN.name);
+    if (P > 0 && (!d.start || !d.target || !d.solution || !d.status))
+        return fail(PIKAMD_EINVAL, "%s: start, target, solution and status must not be NULL", CARTESIAN.name);
+    return 0;
+}
+
+pik::CartesianArgs cartesian_args(const pikamd_cartesian* c, int64_t P, int32_t W, const CartesianArrays& d) {
+    pik::CartesianArgs a = {};
+    a.path = {P, W, 0, d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
+    a.target = d.target;
+    a.goals = d.goals;
+    a.steps = d.steps;
+    a.fraction = d.fraction;
+    a.frame = c->frame;
+    a.min_steps = pik::cartesian_min_steps(c->min_steps, c->jump_factor);
+    a.max_translation = c->max_translation;
+    a.max_rotation = c->max_rotation;
+    a.jump_factor = c->jump_factor;
+    return a;
+}
+
+// The two steps of a call on `st`: the prepare kernel of the flavour pikamd_fk_batch runs in (the handle's), the walk
+// of the flavour a path call with these parameters runs in.
+int run_cartesian(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pik::CartesianArgs& a,
+                  hipStream_t st, int slot) {
+    const int dof = s->chain.dof;
+    const pik::CartesianOps* fk_ops = ops_at<pik::CartesianOps>(flavour_of(s, nullptr, nullptr), FAM_CARTESIAN, dof);
+    const pik::CartesianOps* walk_ops = ops_at<pik::CartesianOps>(flavour_of(s, p, nullptr), FAM_CARTESIAN, dof);
+    if (!fk_ops || !walk_ops) return no_kernels(dof);
+    if (int rc = fk_ops->prepare(s, pk, a, st, slot)) return rc;
+    return walk_ops->walk(s, pk, a, st, slot);
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_interpolate_poses(const pikamd_cartesian* c, int64_t P, int32_t W, const double* start_pose,
+                                 const double* target, double* goals, int32_t* steps) {
+    const char* const who = "pikamd_interpolate_poses";
+    if (int rc = check_cartesian(who, c)) return rc;
+    if (W < 1 || P < 0) return fail(PIKAMD_EINVAL, "%s: %lld paths of %d waypoints: expected P >= 0 and W >= 1", who, (long long)P, (int)W);
+    if (!start_pose || !target || !goals || !steps)
+        return fail(PIKAMD_EINVAL, "%s: start_pose, target, goals and steps must not be NULL", who);
+    const pik_interp::Motion m = motion_of(c);
+    for (int64_t i = 0; i < P; ++i) {
+        double a[7], t[7];
+        for (int e = 0; e < 7; ++e) {
+            a[e] = start_pose[7 * i + e];
+            t[e] = target[7 * i + e];
+        }
+        steps[i] = pik_interp::interpolate_path(m, W, a, t, goals + 7 * i * (int64_t)W);
+    }
+    return 0;
+}
+
+int32_t pikamd_cartesian_paths_device(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                                      int32_t W, const double* d_start, const double* d_target,
+                                      const double* d_max_joint_step, double* d_solution, int32_t* d_status,
+                                      double* d_final_cost, pikamd_stats* d_stats, int32_t* d_reached,
+                                      int32_t* d_steps, double* d_fraction, double* d_goals, void* stream,
+                                      int32_t slot) {
+    CartesianArrays d = {d_start, d_target, d_max_joint_step, d_solution, d_status, d_final_cost,
+                         d_stats, d_reached, d_steps,         d_fraction, d_goals};
+    pik::ParamsK pk;
+    if (int rc = check_cartesian_paths(s, p, c, P, W, d, pk)) return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (P == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    HIP_TRY(hipSetDevice(s->device));
+    if (!d.goals) {
+        // the poses in the slot's scratch, which grows only past the largest earlier call on the slot
+        pik::DevBuf& buf = ext_of(s)->cartesian_goals[slot];
+        if (int rc = buf.ensure(sizeof(double) * 7 * (size_t)P * (size_t)W)) return rc;
+        d.goals = (double*)buf.p;
+    }
+    return run_cartesian(s, p, pk, cartesian_args(c, P, W, d), (hipStream_t)stream, slot);
+}
+
+int32_t pikamd_cartesian_paths(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                               int32_t W, const double* start, const double* target, const double* max_joint_step,
+                               double* solution, int32_t* status, double* final_cost, pikamd_stats* stats,
+                               int32_t* reached, int32_t* steps, double* fraction, double* goals) {
+    const CartesianArrays h = {start, target, max_joint_step, solution, status, final_cost,
+                               stats, reached, steps,          fraction, goals};
+    pik::ParamsK pk;
+    if (int rc = check_cartesian_paths(s, p, c, P, W, h, pk)) return rc;
+    if (P == 0) return 0;
+    if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
+    Staging st(s, CARTESIAN.name);
+    if (int rc = st.begin()) return rc;
+    const size_t d = (size_t)s->chain.dof, paths = (size_t)P, rows = paths * (size_t)W;
+    const int start_ = st.in(h.start, sizeof(double) * d * paths), target_ = st.in(h.target, sizeof(double) * 7 * paths);
+    const int step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes -- the poses apart, which the
+    // walk reads)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), steps_ = st.out(h.steps, sizeof(int32_t) * paths, true);
+    const int fraction_ = st.out(h.fraction, sizeof(double) * paths, false), goals_ = st.out(h.goals, sizeof(double) * 7 * rows, true);
+    if (int rc = st.allocate()) return rc;
+    const CartesianArrays dev = {st.at<const double>(start_), st.at<const double>(target_), st.at<const double>(step),
+                                 st.at<double>(sol),          st.at<int32_t>(status_),      st.at<double>(cost),
+                                 st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_),     st.at<int32_t>(steps_),
+                                 st.at<double>(fraction_),    st.at<double>(goals_)};
+    if (int rc = st.upload()) return rc;
+    return st.finish(run_cartesian(s, p, pk, cartesian_args(c, P, W, dev), st.stream(), Staging::SLOT));
+}
+
+const char* pikamd_cartesian_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
+    if (!s || !p) return "";
+    const Flavour f = flavour_of(s, p, nullptr);
+    pikamd_solver* m = const_cast<pikamd_solver*>(s);
+    const int lanes = pik::path_lanes(s, P, is_exact(f)), dof = s->chain.dof;
+    if (lanes == 1)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_cartesian_kernel<%d>", FLAVOUR_NAMESPACE[f], dof);
+    else
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_cartesian_%s_kernel<%d,%d>", FLAVOUR_NAMESPACE[f],
+                 is_exact(f) ? "team" : "wide", dof, lanes);
+    return m->kernel_name;
 }
 
 } // extern "C"

@@ -157,6 +157,15 @@ struct PathResult {
     std::vector<int32_t> reached; // [P] leading held waypoints: reached / W is computeCartesianPath's fraction
 };
 
+// Solver::compute_cartesian_paths: P Cartesian motions, each walked for its own number of steps
+struct CartesianResult {
+    PathResult paths;              // [P][W] rows; PIKAMD_PATH_RELATIVE_JUMP where the relative test stopped a path;
+                                   // paths.reached [P]: the waypoints that held
+    std::vector<int32_t> steps;    // [P] MoveIt's step count; steps[p] > W: the path was not walked (call again with more)
+    std::vector<double> fraction;  // [P] computeCartesianPath's return value
+    std::vector<Pose> goals;       // [P][W] the poses that were walked
+};
+
 // Solver::ik_gradient_search_batch: local mode with random restarts (ik_memetic_search_batch: global mode)
 struct SearchResult {
     BatchResult batch;                 // what the loop of restarts returned per problem (stats summed over its attempts)
@@ -453,6 +462,51 @@ class Solver {
                                max_joint_step ? max_joint_step->data() : nullptr, r.solution.data(), r.status.data(),
                                r.cost.data(), r.stats.data(), r.reached.data()) != 0)
             throw std::runtime_error(pikamd_last_error());
+        return r;
+    }
+
+    // computeCartesianPath in one call (pikamd_cartesian_paths): start [P][dof] joint states, targets [P] (poses in
+    // the base frame, poses relative to the start tip frame or offsets: cartesian.frame).  The poses are generated on
+    // the device with MoveIt's step count (cartesian.max_translation / max_rotation / min_steps), every path is walked
+    // for its own steps by ik_gradient as ik_gradient_paths does, max_joint_step [dof] (optional) is the absolute jump
+    // threshold and cartesian.jump_factor the relative one.  waypoints: the rows per path; a path that needs more is
+    // reported in steps and not walked.
+    CartesianResult compute_cartesian_paths(const std::vector<double>& start, const std::vector<Pose>& targets,
+                                            int waypoints, const pikamd_cartesian& cartesian, const CostSpec& costs,
+                                            const GradientIkParams& params, bool approx_solution = false,
+                                            const std::vector<double>* max_joint_step = nullptr) const {
+        if (waypoints < 1) throw std::invalid_argument("pick_ik_amd: a path has at least one waypoint");
+        const size_t P = targets.size(), rows = P * static_cast<size_t>(waypoints);
+        if (start.size() != P * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: start size != P * dof");
+        if (max_joint_step && static_cast<int>(max_joint_step->size()) != dof_)
+            throw std::invalid_argument("pick_ik_amd: max_joint_step size != dof");
+        const pikamd_params p = to_params(costs, nullptr, &params, approx_solution);
+        std::vector<double> t7(7 * P), g7(7 * rows);
+        for (size_t b = 0; b < P; ++b) {
+            const Pose& g = targets[b];
+            const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+            for (int k = 0; k < 7; ++k) t7[7 * b + k] = v[k];
+        }
+        CartesianResult r;
+        r.paths.solution.resize(rows * dof_);
+        r.paths.status.resize(rows);
+        r.paths.cost.resize(rows);
+        r.paths.stats.resize(rows);
+        r.paths.reached.resize(P);
+        r.steps.resize(P);
+        r.fraction.resize(P);
+        if (pikamd_cartesian_paths(h_, &p, &cartesian, static_cast<int64_t>(P), waypoints, start.data(), t7.data(),
+                                   max_joint_step ? max_joint_step->data() : nullptr, r.paths.solution.data(),
+                                   r.paths.status.data(), r.paths.cost.data(), r.paths.stats.data(),
+                                   r.paths.reached.data(), r.steps.data(), r.fraction.data(), g7.data()) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        r.goals.resize(rows);
+        for (size_t b = 0; b < rows; ++b) {
+            const double* v = &g7[7 * b];
+            Pose g;
+            g.x = v[0]; g.y = v[1]; g.z = v[2]; g.qw = v[3]; g.qx = v[4]; g.qy = v[5]; g.qz = v[6];
+            r.goals[b] = g;
+        }
         return r;
     }
 

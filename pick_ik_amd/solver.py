@@ -106,6 +106,24 @@ class Gate(C.Structure):
 #: status of an answer the gate refused (PIKAMD_GATE_REFUSED)
 GATE_REFUSED = -1002
 
+#: cartesian_paths: the first waypoint whose joint-space step is further than jump_factor times the mean step
+#: (PIKAMD_PATH_RELATIVE_JUMP)
+PATH_RELATIVE_JUMP = -1003
+#: Cartesian.frame (PIKAMD_CARTESIAN_*): the target is a pose in the base frame / relative to the start tip frame / a
+#: translation added to the start's in the base frame, orientation kept
+CARTESIAN_GLOBAL, CARTESIAN_TIP, CARTESIAN_OFFSET = 0, 1, 2
+
+
+class Cartesian(C.Structure):
+    """pikamd_cartesian: what computeCartesianPath is given beside the start state and the target -- the frame of the
+    target, MaxEEFStep (max_translation, max_rotation; not > 0: not limiting), the minimum step count (0: MoveIt's rule,
+    10 with a relative test and 1 without) and the relative jump threshold factor (not > 0: no relative test)"""
+    _fields_ = [("frame", C.c_int32), ("min_steps", C.c_int32), ("max_translation", C.c_double),
+                ("max_rotation", C.c_double), ("jump_factor", C.c_double)]
+
+    def __init__(self, frame=CARTESIAN_GLOBAL, min_steps=0, max_translation=0.0, max_rotation=0.0, jump_factor=0.0):
+        super().__init__(frame, min_steps, max_translation, max_rotation, jump_factor)
+
 
 class Batch(C.Structure):
     """pikamd_batch: one batch of a multi-batch call (device or host pointers, see the header)."""
@@ -180,6 +198,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_gate_batch", "pikamd_set_approximate_gate",
     "pikamd_search_paths", "pikamd_search_paths_device", "pikamd_search_paths_kernel_name",
     "pikamd_search_global_paths", "pikamd_search_global_paths_device", "pikamd_search_global_paths_kernel_name",
+    "pikamd_interpolate_poses", "pikamd_cartesian_paths", "pikamd_cartesian_paths_device", "pikamd_cartesian_kernel_name",
 )
 
 _libs = {}
@@ -299,6 +318,16 @@ def lib(strict: bool = False):
     L.pikamd_search_global_paths_device.restype = C.c_int32
     L.pikamd_search_global_paths_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
     L.pikamd_search_global_paths_kernel_name.restype = C.c_char_p
+    L.pikamd_interpolate_poses.argtypes = [C.POINTER(Cartesian), C.c_int64, C.c_int32, dp, dp, dp, ip]
+    L.pikamd_interpolate_poses.restype = C.c_int32
+    L.pikamd_cartesian_paths.argtypes = [vp, C.POINTER(Params), C.POINTER(Cartesian), C.c_int64, C.c_int32, dp, dp, dp, dp,
+                                         ip, dp, vp, ip, ip, dp, dp]
+    L.pikamd_cartesian_paths.restype = C.c_int32
+    L.pikamd_cartesian_paths_device.argtypes = [vp, C.POINTER(Params), C.POINTER(Cartesian), C.c_int64, C.c_int32, vp, vp,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32]
+    L.pikamd_cartesian_paths_device.restype = C.c_int32
+    L.pikamd_cartesian_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
+    L.pikamd_cartesian_kernel_name.restype = C.c_char_p
     up = C.POINTER(C.c_uint32)
     L.pikamd_debug_regime.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, ip, up, up, ip]
     L.pikamd_debug_regime.restype = C.c_int32
@@ -745,6 +774,68 @@ class Solver:
         self._env_options()
         return self._L.pikamd_path_kernel_name(self._h, C.byref(params), P).decode()
 
+    # ---- computeCartesianPath in one call ---------------------------------------------------
+    def cartesian_paths(self, params: Params, cartesian: Cartesian, start, target, W: int, max_joint_step=None,
+                        optional: bool = True):
+        """pikamd_cartesian_paths: P Cartesian motions in local mode (params.mode = 1), each from the start joint state
+        start[p] to target[p] (a pose or an offset, cartesian.frame).  The poses are generated on the device, every
+        path is walked for its own number of steps (steps[p]; a path with steps[p] > W is not walked: call again with
+        a larger W), the absolute (max_joint_step) and the relative (cartesian.jump_factor) jump tests are applied and
+        MoveIt's fraction comes out.  start [P][dof], target [P][7], max_joint_step [dof] or None.  Returns (solution
+        [P][W][dof], status [P][W], cost [P][W], stats [P][W], reached [P], steps [P], fraction [P], goals [P][W][7]);
+        optional=False leaves out every array the library can do without (cost, stats, reached, fraction and goals are
+        None then).  The result is what fk + interpolate_poses + the loop of solve_paths calls in
+        include/pick_ik_amd.h returns, bit for bit."""
+        self._env_options()
+        start = _f64(start)
+        if start.ndim != 2 or start.shape[1] != self.dof:
+            raise ValueError(f"start: expected [P][{self.dof}], got {list(start.shape)}")
+        P = start.shape[0]
+        target = _f64(target)
+        if target.shape != (P, 7):
+            raise ValueError(f"target: expected [{P}][7], got {list(target.shape)}")
+        W = int(W)
+        if W < 1:
+            raise ValueError("W: a path has at least one waypoint")
+        step = None
+        if max_joint_step is not None:
+            step = _f64(max_joint_step)
+            if step.shape != (self.dof,):
+                raise ValueError(f"max_joint_step: expected [{self.dof}], got {list(step.shape)}")
+        sol = np.empty((P, W, self.dof))
+        status = np.empty((P, W), dtype=np.int32)
+        steps = np.empty(P, dtype=np.int32)
+        cost = np.empty((P, W)) if optional else None
+        stats = np.zeros((P, W), dtype=STATS_DTYPE) if optional else None
+        reached = np.empty(P, dtype=np.int32) if optional else None
+        fraction = np.empty(P) if optional else None
+        goals = np.empty((P, W, 7)) if optional else None
+        self._chk(self._L.pikamd_cartesian_paths(
+            self._h, C.byref(params), C.byref(cartesian), P, W, _dp(start), _dp(target),
+            None if step is None else _dp(step), _dp(sol), _ip(status), _dp(cost) if optional else None,
+            stats.ctypes.data_as(C.c_void_p) if optional else None, _ip(reached) if optional else None, _ip(steps),
+            _dp(fraction) if optional else None, _dp(goals) if optional else None))
+        return sol, status, cost, stats, reached, steps, fraction, goals
+
+    def cartesian_paths_device(self, params: Params, cartesian: Cartesian, P: int, W: int, d_start: int, d_target: int,
+                               d_solution: int, d_status: int, d_steps: int, d_max_joint_step: int = 0, d_cost: int = 0,
+                               d_stats: int = 0, d_reached: int = 0, d_fraction: int = 0, d_goals: int = 0,
+                               stream: int = 0, slot: int = 0):
+        """Enqueue cartesian_paths on HBM-resident buffers (raw device addresses); returns immediately -- the caller
+        synchronises the stream.  Without d_goals the poses are kept in scratch of the handle's slot."""
+        self._env_options()
+        if P < 0 or W < 1:
+            raise ValueError(f"{P} paths of {W} waypoints: expected P >= 0 and W >= 1")
+        self._chk(self._L.pikamd_cartesian_paths_device(
+            self._h, C.byref(params), C.byref(cartesian), P, W, d_start or None, d_target or None,
+            d_max_joint_step or None, d_solution or None, d_status or None, d_cost or None, d_stats or None,
+            d_reached or None, d_steps or None, d_fraction or None, d_goals or None, stream or None, slot))
+
+    def cartesian_kernel_name(self, params: Params, P: int) -> str:
+        """the kernel that walks P paths of cartesian_paths (pikamd_cartesian_kernel_name)"""
+        self._env_options()
+        return self._L.pikamd_cartesian_kernel_name(self._h, C.byref(params), P).decode()
+
     # ---- Cartesian paths from a pose: the start state restarted until the path holds -------
     def search_paths(self, params: Params, goals, seed, max_attempts: int, max_joint_step=None, rng_seed: int = 0,
                      problem_offset: int = 0, initial_guess=None):
@@ -946,6 +1037,28 @@ class Solver:
         n = C.c_int32(0)
         name = self._L.pikamd_search_kernel_name(self._h, C.byref(params), B, max_attempts, C.byref(n)).decode()
         return name, int(n.value)
+
+
+def interpolate_poses(cartesian: Cartesian, start_pose, target, W: int, strict: bool = False):
+    """pikamd_interpolate_poses (a host function: no handle, no device): the waypoints of P Cartesian motions from
+    start_pose [P][7] to target [P][7] (cartesian.frame says what a target is).  Returns (goals [P][W][7], steps [P]):
+    steps[p] is MoveIt's step count, rows k < steps[p] are the interpolated poses, the rows behind them -- and every
+    row of a path with steps[p] > W -- the resolved target."""
+    start_pose = _f64(start_pose)
+    if start_pose.ndim != 2 or start_pose.shape[1] != 7:
+        raise ValueError(f"start_pose: expected [P][7], got {list(start_pose.shape)}")
+    P = start_pose.shape[0]
+    target = _f64(target)
+    if target.shape != (P, 7):
+        raise ValueError(f"target: expected [{P}][7], got {list(target.shape)}")
+    W = int(W)
+    if W < 1:
+        raise ValueError("W: a path has at least one waypoint")
+    goals = np.empty((P, W, 7))
+    steps = np.empty(P, dtype=np.int32)
+    L = lib(strict)
+    _check(L.pikamd_interpolate_poses(C.byref(cartesian), P, W, _dp(start_pose), _dp(target), _dp(goals), _ip(steps)), L)
+    return goals, steps
 
 
 def shard_bounds(total: int, rank: int, world: int, strict: bool = False):
