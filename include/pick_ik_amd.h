@@ -863,6 +863,83 @@ int32_t pikamd_cartesian_paths_device(pikamd_solver* s, const pikamd_params* p, 
                                       int32_t* d_steps, double* d_fraction, double* d_goals, void* stream,
                                       int32_t slot);
 const char* pikamd_cartesian_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
+/* ---- computeCartesianPath through waypoints ---------------------------------------------------------------
+ * MoveIt's computeCartesianPath has a second overload: a LIST of waypoints per motion (approach - grasp - retreat,
+ * corners, anything that is not one straight line).  Segment i starts at the tip pose of the joint state segment i-1
+ * ended in -- that is not waypoint i-1 itself --, so its poses and its step count exist only once segment i-1 has been
+ * solved.  With pikamd_cartesian_paths that is S dependent calls, each staged and synchronised, the complete paths
+ * picked and repacked on the host between them, and the relative jump test -- which MoveIt applies ONCE, to the
+ * stitched trajectory -- redone by hand.  Here P motions of up to S targets each go in and one call does it, with no
+ * host round trip between the segments.
+ *
+ * pikamd_cartesian_waypoints.  p->mode must be 1.  pikamd_cartesian is reused unchanged.  The result is DEFINED by the
+ * entry points above, bit for bit:
+ *
+ *   c1 = *c with jump_factor = 0     (MoveIt walks every segment of a waypoint list with NO jump test, so min_steps = 0
+ *                                     resolves to 1 here, never to 10; a min_steps > 0 holds for every segment)
+ *   for every p:  S_p = n_targets ? clamp(n_targets[p], 0, S) : S
+ *     every row = (start[p], PIKAMD_NOT_ATTEMPTED, 0, zero); every goals row = seven zeros; segment_steps[p][*] = 0
+ *     cur = start[p]; off = 0; held = 0; frac = 0.0; need = 0
+ *     for i in 0 .. S_p-1:
+ *       room = W - off
+ *       if room == 0: n_i = the steps of pikamd_interpolate_poses(c1, 1, 1, pikamd_fk_batch(cur), targets[p][i])
+ *       else:         (rows, n_i, r_i, g) = pikamd_cartesian_paths(p, c1, P = 1, W = room, start = cur, targets[p][i],
+ *                                                                  max_joint_step)
+ *       segment_steps[p][i] = n_i;  need = off + n_i, saturating at INT32_MAX
+ *       if room > 0: goals rows off..W-1 = g                  (a segment that does not fit: every one of them its target)
+ *       if n_i > room:                 rows off..W-1 = (cur, NOT_ATTEMPTED, 0, zero); stop       (did not fit; frac stays)
+ *       rows off..W-1 = rows                                   (the next segment overwrites what lies behind n_i)
+ *       held = off + r_i
+ *       if r_i == n_i: frac = (double)(i+1) / (double)S_p; cur = solution row off+n_i-1; off += n_i
+ *       else:          frac = (double)i / (double)S_p + ((double)r_i / (double)n_i) / (double)S_p; stop
+ *     steps[p] = need;  r = held
+ *     if c->jump_factor > 0 and r >= 1: the relative test of pikamd_cartesian_paths, statement for statement, over
+ *        traj[0] = start[p], traj[j] = solution[p][j-1], j = 1..r   (fraction = frac * (i+1)/(r+1), row i =
+ *        PIKAMD_PATH_RELATIVE_JUMP, rows behind it blank with traj[i], r = i)
+ *     reached[p] = r;  fraction[p] = the result
+ *
+ * Every floating-point operation is rounded on its own.  Consequences:
+ *   - S = 1 with jump_factor not > 0 is pikamd_cartesian_paths, array for array (segment_steps[p][0] = steps[p]).
+ *   - S = 1 with jump_factor > 0 is pikamd_cartesian_paths when min_steps > 0 is given explicitly.  With min_steps = 0
+ *     the two differ in MoveIt's minimum: 1 here, 10 there.  That is MoveIt's own behaviour for a waypoint list.
+ *   - In the TIP and OFFSET frames target i is relative to the tip pose of the state segment i-1 ended in.
+ *   - The absolute thresholds are the caller's max_joint_step, applied while walking: the departure
+ *     pikamd_cartesian_paths already has.
+ *   - S_p = 0 gives reached 0, steps 0, fraction 0.
+ *   - steps[p] > W means: call again with W >= steps[p] (when the segment that did not fit was not the last, again
+ *     until it holds).  The rows in front of the segment that did not fit are valid.
+ *   - The handle's approximate-solution gate is NOT applied.
+ *   start [P][dof], targets [P][S][7] (meaning per c->frame), n_targets [P] (may be NULL: S for every path; values are
+ *   clamped to 0..S), max_joint_step [dof] (may be NULL), solution [P][W][dof], status [P][W], final_cost [P][W] (may be
+ *   NULL), stats [P][W] (may be NULL), reached [P] (may be NULL), steps [P] (REQUIRED: the rows the path needs in all),
+ *   segment_steps [P][S] (may be NULL: the step count of every segment started, 0 for the others), fraction [P] (may be
+ *   NULL), goals [P][W][7] (may be NULL): the poses that were walked.
+ * Refused: several tip frames (PIKAMD_EUNSUPPORTED); everything pikamd_cartesian_paths refuses, S < 1, S > W (every
+ * segment needs at least one row) and a NULL targets (PIKAMD_EINVAL).  P = 0 returns 0.  No plugin-shim entry
+ * (KinematicsBase has none).
+ * pikamd_cartesian_waypoints: host pointers; synchronous, staged through the library's own pinned buffers and stream
+ * like pikamd_cartesian_paths, behind the same automatic self test of the local-mode kernels; honours lanes_per_elite
+ * as pikamd_solve_paths does.  pikamd_cartesian_waypoints_device: device pointers (n_targets and max_joint_step too);
+ * enqueues S passes -- a segment kernel (forward kinematics of the current state, poses, steps) and the walk of the
+ * segment -- and a finish kernel (blank rows, relative test, reached, steps, fraction) on `stream` and returns without
+ * synchronising, no self test (see pikamd_solve_batch_device for `slot`).  A pass in which no path is open finds
+ * nothing to walk.  The per-path state of the passes and, without d_goals, the poses are kept in scratch that belongs
+ * to the handle's slot; it grows only when a call needs more than any earlier call on that slot did (a grow frees,
+ * and a free synchronises the device: run the largest call first where that matters).
+ * pikamd_cartesian_waypoints_kernel_name: the kernel that walks the segments of P paths (see pikamd_kernel_name), e.g.
+ * `pik_exact::ik_polyline_team_kernel<7,16>`. */
+int32_t pikamd_cartesian_waypoints(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                                   int32_t S, int32_t W, const double* start, const double* targets,
+                                   const int32_t* n_targets, const double* max_joint_step, double* solution,
+                                   int32_t* status, double* final_cost, pikamd_stats* stats, int32_t* reached,
+                                   int32_t* steps, int32_t* segment_steps, double* fraction, double* goals);
+int32_t pikamd_cartesian_waypoints_device(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                                          int32_t S, int32_t W, const double* d_start, const double* d_targets,
+                                          const int32_t* d_n_targets, const double* d_max_joint_step, double* d_solution,
+                                          int32_t* d_status, double* d_final_cost, pikamd_stats* d_stats,
+                                          int32_t* d_reached, int32_t* d_steps, int32_t* d_segment_steps,
+                                          double* d_fraction, double* d_goals, void* stream, int32_t slot);
+const char* pikamd_cartesian_waypoints_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -20,6 +20,7 @@
 #include "pik_globalpath_ops.hpp"
 #include "pik_interp.hpp"
 #include "pik_path_ops.hpp"
+#include "pik_polyline_ops.hpp"
 #include "pik_restart_ops.hpp"
 #include "pik_route_ops.hpp"
 #include "pik_search_ops.hpp"
@@ -52,6 +53,7 @@ PIK_DECLARE_OPS_FAMILY(void, restart)
 PIK_DECLARE_OPS_FAMILY(void, startpath)
 PIK_DECLARE_OPS_FAMILY(void, globalpath)
 PIK_DECLARE_OPS_FAMILY(void, cartesian)
+PIK_DECLARE_OPS_FAMILY(void, polyline)
 } // namespace pik_exact
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
@@ -87,7 +89,7 @@ enum Flavour {
 #endif
     N_FLAVOURS
 };
-enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, N_FAMILIES };
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, FAM_POLYLINE, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -117,6 +119,9 @@ struct SolverExt : pikamd_solver {
     pik::DevBuf globalpath_rows[pik::N_SLOTS];
     // pikamd_cartesian_paths_device: per slot the interpolated poses of a call whose caller keeps none
     pik::DevBuf cartesian_goals[pik::N_SLOTS];
+    // pikamd_cartesian_waypoints*: per slot the per-path state of the passes and, for a call whose caller keeps none,
+    // the interpolated poses
+    pik::DevBuf polyline_rows[pik::N_SLOTS];
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -140,12 +145,13 @@ const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
      untyped<pik::RouteOps, pik::route_ops>,
 #endif
      untyped<pik::RestartOps, pik::restart_ops>, untyped<pik::StartPathOps, pik::startpath_ops>,
-     untyped<pik::GlobalPathOps, pik::globalpath_ops>, untyped<pik::CartesianOps, pik::cartesian_ops>},
+     untyped<pik::GlobalPathOps, pik::globalpath_ops>, untyped<pik::CartesianOps, pik::cartesian_ops>,
+     untyped<pik::PolylineOps, pik::polyline_ops>},
 #if !defined(PIK_STRICT)
     {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops,
-     pik_exact::startpath_ops, pik_exact::globalpath_ops, pik_exact::cartesian_ops},
-    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr},
-    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr},
+     pik_exact::startpath_ops, pik_exact::globalpath_ops, pik_exact::cartesian_ops, pik_exact::polyline_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr, nullptr},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr, nullptr},
 #endif
 };
 // ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
@@ -522,6 +528,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : ext_of(s)->restart_rows) b.release();
     for (auto& b : ext_of(s)->startpath_rows) b.release();
     for (auto& b : ext_of(s)->cartesian_goals) b.release();
+    for (auto& b : ext_of(s)->polyline_rows) b.release();
     for (auto& b : ext_of(s)->globalpath_rows) b.release();
     ext_of(s)->gate_params_dev.release();
     for (auto& j : s->jobs) {
@@ -1535,7 +1542,7 @@ class Staging {
     pikamd_solver* s_;
     const char* who_;
     pik::HostJob& J_;
-    Region r_[12]; // (pikamd_search_paths registers 11)
+    Region r_[13]; // (pikamd_cartesian_waypoints registers 13)
     int n_ = 0;
     size_t in_bytes_ = 0, total_ = 0;
 };
@@ -2381,6 +2388,150 @@ const char* pikamd_cartesian_kernel_name(const pikamd_solver* s, const pikamd_pa
         snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_cartesian_kernel<%d>", FLAVOUR_NAMESPACE[f], dof);
     else
         snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_cartesian_%s_kernel<%d,%d>", FLAVOUR_NAMESPACE[f],
+                 is_exact(f) ? "team" : "wide", dof, lanes);
+    return m->kernel_name;
+}
+
+} // extern "C"
+
+// ---- computeCartesianPath through waypoints (pik_polyline.hpp) ---------------------------------------
+namespace {
+
+const CallKind WAYPOINTS = {"pikamd_cartesian_waypoints", 1, "Cartesian motions are walked in local mode (mode = 1)", "", true,
+                            "[P][W][dof]", "start"};
+
+// the arrays of a pikamd_cartesian_waypoints call: host pointers, or device pointers
+struct WaypointArrays {
+    const double *start, *targets;
+    const int32_t* n_targets;
+    const double* max_step;
+    double* solution;
+    int32_t* status;
+    double* cost;
+    pikamd_stats* stats;
+    int32_t *reached, *steps, *segment_steps;
+    double *fraction, *goals;
+};
+
+// what both entry points refuse: pikamd_cartesian_paths' list, then the target list's own
+int check_cartesian_waypoints(const pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P, int32_t S,
+                              int32_t W, const WaypointArrays& d, pik::ParamsK& pk) {
+    const char* const who = WAYPOINTS.name;
+    if (int rc = check_call(WAYPOINTS, s, p, P, W, false, pk)) return rc;
+    if (int rc = check_cartesian(who, c)) return rc;
+    if (s->n_tips > 1)
+        return fail(PIKAMD_EUNSUPPORTED, "%s: %d tip frames: a Cartesian motion is that of one tip frame", who, s->n_tips);
+    if (!d.steps) return fail(PIKAMD_EINVAL, "%s: steps must not be NULL (a path with steps[p] > W has a segment that did not fit)", who);
+    if (S < 1) return fail(PIKAMD_EINVAL, "%s: %d targets per path: expected S >= 1", who, (int)S);
+    if (S > W) return fail(PIKAMD_EINVAL, "%s: %d targets in %d rows: expected S <= W (every segment needs a row)", who, (int)S, (int)W);
+    if (P > 0 && (!d.start || !d.targets || !d.solution || !d.status))
+        return fail(PIKAMD_EINVAL, "%s: start, targets, solution and status must not be NULL", who);
+    return 0;
+}
+
+// The passes of a call on `st`: per segment the segment kernel of the flavour pikamd_fk_batch runs in (the handle's)
+// and the walk of the flavour a path call with these parameters runs in; the finish behind them.  `state`: the
+// per-path state (polyline_state_bytes) in the slot's scratch.
+int run_polyline(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pikamd_cartesian* c, int64_t P,
+                 int32_t S, int32_t W, const WaypointArrays& d, void* state, hipStream_t st, int slot) {
+    const int dof = s->chain.dof;
+    const pik::PolylineOps* fk_ops = ops_at<pik::PolylineOps>(flavour_of(s, nullptr, nullptr), FAM_POLYLINE, dof);
+    const pik::PolylineOps* walk_ops = ops_at<pik::PolylineOps>(flavour_of(s, p, nullptr), FAM_POLYLINE, dof);
+    if (!fk_ops || !walk_ops) return no_kernels(dof);
+    pik::PolylineArgs a = {};
+    a.path = {P, W, 0, d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
+    a.targets = d.targets;
+    a.n_targets = d.n_targets;
+    a.goals = d.goals;
+    a.steps = d.steps;
+    a.segment_steps = d.segment_steps;
+    a.fraction = d.fraction;
+    a.st = pik::polyline_state_at(state, P);
+    a.S = S;
+    a.frame = c->frame;
+    a.min_steps = pik::cartesian_min_steps(c->min_steps, 0.0); // (no jump test per segment: MoveIt's minimum is 1)
+    a.max_translation = c->max_translation;
+    a.max_rotation = c->max_rotation;
+    a.jump_factor = c->jump_factor;
+    for (int i = 0; i < S; ++i) {
+        a.seg = i;
+        if (int rc = fk_ops->segment(s, pk, a, st, slot)) return rc;
+        if (int rc = walk_ops->walk(s, pk, a, st, slot)) return rc;
+    }
+    return walk_ops->finish(s, pk, a, st, slot);
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t pikamd_cartesian_waypoints_device(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                                          int32_t S, int32_t W, const double* d_start, const double* d_targets,
+                                          const int32_t* d_n_targets, const double* d_max_joint_step, double* d_solution,
+                                          int32_t* d_status, double* d_final_cost, pikamd_stats* d_stats,
+                                          int32_t* d_reached, int32_t* d_steps, int32_t* d_segment_steps,
+                                          double* d_fraction, double* d_goals, void* stream, int32_t slot) {
+    WaypointArrays d = {d_start,  d_targets, d_n_targets, d_max_joint_step, d_solution,  d_status,  d_final_cost,
+                        d_stats,  d_reached, d_steps,     d_segment_steps,  d_fraction,  d_goals};
+    pik::ParamsK pk;
+    if (int rc = check_cartesian_waypoints(s, p, c, P, S, W, d, pk)) return rc;
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (P == 0) return 0;
+    // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
+    HIP_TRY(hipSetDevice(s->device));
+    // the per-path state and, without d_goals, the poses in the slot's scratch, which grows only past the largest
+    // earlier call on the slot
+    const size_t state = align8(pik::polyline_state_bytes(P));
+    pik::DevBuf& buf = ext_of(s)->polyline_rows[slot];
+    if (int rc = buf.ensure(state + (d.goals ? 0 : sizeof(double) * 7 * (size_t)P * (size_t)W))) return rc;
+    if (!d.goals) d.goals = reinterpret_cast<double*>((char*)buf.p + state);
+    return run_polyline(s, p, pk, c, P, S, W, d, buf.p, (hipStream_t)stream, slot);
+}
+
+int32_t pikamd_cartesian_waypoints(pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P,
+                                   int32_t S, int32_t W, const double* start, const double* targets,
+                                   const int32_t* n_targets, const double* max_joint_step, double* solution,
+                                   int32_t* status, double* final_cost, pikamd_stats* stats, int32_t* reached,
+                                   int32_t* steps, int32_t* segment_steps, double* fraction, double* goals) {
+    const WaypointArrays h = {start, targets, n_targets, max_joint_step, solution, status, final_cost,
+                              stats, reached, steps,     segment_steps,  fraction, goals};
+    pik::ParamsK pk;
+    if (int rc = check_cartesian_waypoints(s, p, c, P, S, W, h, pk)) return rc;
+    if (P == 0) return 0;
+    if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
+    Staging st(s, WAYPOINTS.name);
+    if (int rc = st.begin()) return rc;
+    const size_t d = (size_t)s->chain.dof, paths = (size_t)P, rows = paths * (size_t)W, segs = paths * (size_t)S;
+    const int start_ = st.in(h.start, sizeof(double) * d * paths), targets_ = st.in(h.targets, sizeof(double) * 7 * segs);
+    const int count = st.in(h.n_targets, sizeof(int32_t) * paths), step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes -- the poses apart, which the
+    // walk reads)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), steps_ = st.out(h.steps, sizeof(int32_t) * paths, true);
+    const int segsteps = st.out(h.segment_steps, sizeof(int32_t) * segs, false);
+    const int fraction_ = st.out(h.fraction, sizeof(double) * paths, false), goals_ = st.out(h.goals, sizeof(double) * 7 * rows, true);
+    if (int rc = st.allocate()) return rc;
+    pik::DevBuf& state = ext_of(s)->polyline_rows[Staging::SLOT];
+    if (int rc = state.ensure(pik::polyline_state_bytes(P))) return rc;
+    const WaypointArrays dev = {st.at<const double>(start_), st.at<const double>(targets_), st.at<const int32_t>(count),
+                                st.at<const double>(step),   st.at<double>(sol),            st.at<int32_t>(status_),
+                                st.at<double>(cost),         st.at<pikamd_stats>(stats_),   st.at<int32_t>(reached_),
+                                st.at<int32_t>(steps_),      st.at<int32_t>(segsteps),      st.at<double>(fraction_),
+                                st.at<double>(goals_)};
+    if (int rc = st.upload()) return rc;
+    return st.finish(run_polyline(s, p, pk, c, P, S, W, dev, state.p, st.stream(), Staging::SLOT));
+}
+
+const char* pikamd_cartesian_waypoints_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
+    if (!s || !p) return "";
+    const Flavour f = flavour_of(s, p, nullptr);
+    pikamd_solver* m = const_cast<pikamd_solver*>(s);
+    const int lanes = pik::path_lanes(s, P, is_exact(f)), dof = s->chain.dof;
+    if (lanes == 1)
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_polyline_kernel<%d>", FLAVOUR_NAMESPACE[f], dof);
+    else
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_polyline_%s_kernel<%d,%d>", FLAVOUR_NAMESPACE[f],
                  is_exact(f) ? "team" : "wide", dof, lanes);
     return m->kernel_name;
 }

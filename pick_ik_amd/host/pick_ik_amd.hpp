@@ -166,6 +166,14 @@ struct CartesianResult {
     std::vector<Pose> goals;       // [P][W] the poses that were walked
 };
 
+// Solver::compute_cartesian_waypoints: P Cartesian motions through a list of targets each
+struct CartesianWaypointsResult {
+    CartesianResult cartesian;          // as compute_cartesian_paths gives it, over the stitched rows; steps [P]: the rows
+                                        // the path needs in all (steps[p] > W: a segment did not fit, call again with more)
+    int max_targets = 0;                // S: the longest list
+    std::vector<int32_t> segment_steps; // [P][S] the step count of every segment started, 0 for the others
+};
+
 // Solver::ik_gradient_search_batch: local mode with random restarts (ik_memetic_search_batch: global mode)
 struct SearchResult {
     BatchResult batch;                 // what the loop of restarts returned per problem (stats summed over its attempts)
@@ -506,6 +514,64 @@ class Solver {
             Pose g;
             g.x = v[0]; g.y = v[1]; g.z = v[2]; g.qw = v[3]; g.qx = v[4]; g.qy = v[5]; g.qz = v[6];
             r.goals[b] = g;
+        }
+        return r;
+    }
+
+    // computeCartesianPath through waypoints (pikamd_cartesian_waypoints): start [P][dof] joint states, targets [P]
+    // lists of poses or offsets (cartesian.frame; in the tip and offset frames each relative to the tip pose of the
+    // state the segment before it ended in).  The lists may be of different lengths (the longest gives S, the others
+    // become n_targets); every list needs a row per target at least (waypoints >= S).  Segment after segment is
+    // interpolated and walked on the device, the relative test (cartesian.jump_factor) is applied once to the stitched
+    // rows.  The MoveIt plugin shim has no entry for this: KinematicsBase has none.
+    CartesianWaypointsResult compute_cartesian_waypoints(const std::vector<double>& start,
+                                                         const std::vector<std::vector<Pose>>& targets, int waypoints,
+                                                         const pikamd_cartesian& cartesian, const CostSpec& costs,
+                                                         const GradientIkParams& params, bool approx_solution = false,
+                                                         const std::vector<double>* max_joint_step = nullptr) const {
+        const size_t P = targets.size(), rows = P * static_cast<size_t>(waypoints > 0 ? waypoints : 0);
+        size_t S = 1;
+        for (const std::vector<Pose>& list : targets) S = list.size() > S ? list.size() : S;
+        if (waypoints < 1 || S > static_cast<size_t>(waypoints))
+            throw std::invalid_argument("pick_ik_amd: a waypoint list needs a row per target at least");
+        if (start.size() != P * static_cast<size_t>(dof_)) throw std::invalid_argument("pick_ik_amd: start size != P * dof");
+        if (max_joint_step && static_cast<int>(max_joint_step->size()) != dof_)
+            throw std::invalid_argument("pick_ik_amd: max_joint_step size != dof");
+        const pikamd_params p = to_params(costs, nullptr, &params, approx_solution);
+        std::vector<double> t7(7 * P * S, 0.0), g7(7 * rows);
+        std::vector<int32_t> count(P);
+        for (size_t b = 0; b < P; ++b) {
+            count[b] = static_cast<int32_t>(targets[b].size());
+            for (size_t i = 0; i < targets[b].size(); ++i) {
+                const Pose& g = targets[b][i];
+                const double v[7] = {g.x, g.y, g.z, g.qw, g.qx, g.qy, g.qz};
+                for (int k = 0; k < 7; ++k) t7[7 * (b * S + i) + k] = v[k];
+            }
+        }
+        CartesianWaypointsResult r;
+        r.cartesian.paths.solution.resize(rows * dof_);
+        r.cartesian.paths.status.resize(rows);
+        r.cartesian.paths.cost.resize(rows);
+        r.cartesian.paths.stats.resize(rows);
+        r.cartesian.paths.reached.resize(P);
+        r.cartesian.steps.resize(P);
+        r.cartesian.fraction.resize(P);
+        r.max_targets = static_cast<int>(S);
+        r.segment_steps.resize(P * S);
+        if (pikamd_cartesian_waypoints(h_, &p, &cartesian, static_cast<int64_t>(P), static_cast<int32_t>(S), waypoints,
+                                       start.data(), t7.data(), count.data(),
+                                       max_joint_step ? max_joint_step->data() : nullptr, r.cartesian.paths.solution.data(),
+                                       r.cartesian.paths.status.data(), r.cartesian.paths.cost.data(),
+                                       r.cartesian.paths.stats.data(), r.cartesian.paths.reached.data(),
+                                       r.cartesian.steps.data(), r.segment_steps.data(), r.cartesian.fraction.data(),
+                                       g7.data()) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        r.cartesian.goals.resize(rows);
+        for (size_t b = 0; b < rows; ++b) {
+            const double* v = &g7[7 * b];
+            Pose g;
+            g.x = v[0]; g.y = v[1]; g.z = v[2]; g.qw = v[3]; g.qx = v[4]; g.qy = v[5]; g.qz = v[6];
+            r.cartesian.goals[b] = g;
         }
         return r;
     }

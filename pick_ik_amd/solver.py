@@ -199,6 +199,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_search_paths", "pikamd_search_paths_device", "pikamd_search_paths_kernel_name",
     "pikamd_search_global_paths", "pikamd_search_global_paths_device", "pikamd_search_global_paths_kernel_name",
     "pikamd_interpolate_poses", "pikamd_cartesian_paths", "pikamd_cartesian_paths_device", "pikamd_cartesian_kernel_name",
+    "pikamd_cartesian_waypoints", "pikamd_cartesian_waypoints_device", "pikamd_cartesian_waypoints_kernel_name",
 )
 
 _libs = {}
@@ -328,6 +329,15 @@ def lib(strict: bool = False):
     L.pikamd_cartesian_paths_device.restype = C.c_int32
     L.pikamd_cartesian_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
     L.pikamd_cartesian_kernel_name.restype = C.c_char_p
+    L.pikamd_cartesian_waypoints.argtypes = [vp, C.POINTER(Params), C.POINTER(Cartesian), C.c_int64, C.c_int32, C.c_int32,
+                                             dp, dp, ip, dp, dp, ip, dp, vp, ip, ip, ip, dp, dp]
+    L.pikamd_cartesian_waypoints.restype = C.c_int32
+    L.pikamd_cartesian_waypoints_device.argtypes = [vp, C.POINTER(Params), C.POINTER(Cartesian), C.c_int64, C.c_int32,
+                                                    C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    C.c_int32]
+    L.pikamd_cartesian_waypoints_device.restype = C.c_int32
+    L.pikamd_cartesian_waypoints_kernel_name.argtypes = [vp, C.POINTER(Params), C.c_int64]
+    L.pikamd_cartesian_waypoints_kernel_name.restype = C.c_char_p
     up = C.POINTER(C.c_uint32)
     L.pikamd_debug_regime.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, ip, up, up, ip]
     L.pikamd_debug_regime.restype = C.c_int32
@@ -835,6 +845,79 @@ class Solver:
         """the kernel that walks P paths of cartesian_paths (pikamd_cartesian_kernel_name)"""
         self._env_options()
         return self._L.pikamd_cartesian_kernel_name(self._h, C.byref(params), P).decode()
+
+    # ---- computeCartesianPath through waypoints ---------------------------------------------
+    def cartesian_waypoints(self, params: Params, cartesian: Cartesian, start, targets, W: int, n_targets=None,
+                            max_joint_step=None, optional: bool = True):
+        """pikamd_cartesian_waypoints: P Cartesian motions in local mode (params.mode = 1), each from the start joint
+        state start[p] through the targets targets[p][0..n_targets[p]-1] (poses or offsets, cartesian.frame; in the tip
+        and offset frames relative to the tip pose of the state the previous segment ended in).  Segment after segment
+        is interpolated and walked on the device with no host round trip; the relative jump test is applied once, to
+        the stitched rows.  start [P][dof], targets [P][S][7], n_targets [P] or None (S for every path),
+        max_joint_step [dof] or None, W >= S rows per path.  Returns (solution [P][W][dof], status [P][W], cost [P][W],
+        stats [P][W], reached [P], steps [P], fraction [P], goals [P][W][7], segment_steps [P][S]); steps[p] > W: a
+        segment did not fit, call again with W >= steps[p].  optional=False leaves out every array the library can do
+        without (cost, stats, reached, fraction, goals and segment_steps are None then).  The result is what the loop
+        of cartesian_paths calls in include/pick_ik_amd.h returns, bit for bit."""
+        self._env_options()
+        start = _f64(start)
+        if start.ndim != 2 or start.shape[1] != self.dof:
+            raise ValueError(f"start: expected [P][{self.dof}], got {list(start.shape)}")
+        P = start.shape[0]
+        targets = _f64(targets)
+        if targets.ndim != 3 or targets.shape[0] != P or targets.shape[2] != 7:
+            raise ValueError(f"targets: expected [{P}][S][7], got {list(targets.shape)}")
+        S, W = targets.shape[1], int(W)
+        if S < 1 or W < S:
+            raise ValueError(f"{S} targets in {W} rows: expected W >= S >= 1 (every segment needs a row)")
+        count = None
+        if n_targets is not None:
+            count = np.ascontiguousarray(n_targets, dtype=np.int32)
+            if count.shape != (P,):
+                raise ValueError(f"n_targets: expected [{P}], got {list(count.shape)}")
+        step = None
+        if max_joint_step is not None:
+            step = _f64(max_joint_step)
+            if step.shape != (self.dof,):
+                raise ValueError(f"max_joint_step: expected [{self.dof}], got {list(step.shape)}")
+        sol = np.empty((P, W, self.dof))
+        status = np.empty((P, W), dtype=np.int32)
+        steps = np.empty(P, dtype=np.int32)
+        cost = np.empty((P, W)) if optional else None
+        stats = np.zeros((P, W), dtype=STATS_DTYPE) if optional else None
+        reached = np.empty(P, dtype=np.int32) if optional else None
+        fraction = np.empty(P) if optional else None
+        goals = np.empty((P, W, 7)) if optional else None
+        segment_steps = np.empty((P, S), dtype=np.int32) if optional else None
+        self._chk(self._L.pikamd_cartesian_waypoints(
+            self._h, C.byref(params), C.byref(cartesian), P, S, W, _dp(start), _dp(targets),
+            None if count is None else _ip(count), None if step is None else _dp(step), _dp(sol), _ip(status),
+            _dp(cost) if optional else None, stats.ctypes.data_as(C.c_void_p) if optional else None,
+            _ip(reached) if optional else None, _ip(steps), _ip(segment_steps) if optional else None,
+            _dp(fraction) if optional else None, _dp(goals) if optional else None))
+        return sol, status, cost, stats, reached, steps, fraction, goals, segment_steps
+
+    def cartesian_waypoints_device(self, params: Params, cartesian: Cartesian, P: int, S: int, W: int, d_start: int,
+                                   d_targets: int, d_solution: int, d_status: int, d_steps: int, d_n_targets: int = 0,
+                                   d_max_joint_step: int = 0, d_cost: int = 0, d_stats: int = 0, d_reached: int = 0,
+                                   d_segment_steps: int = 0, d_fraction: int = 0, d_goals: int = 0, stream: int = 0,
+                                   slot: int = 0):
+        """Enqueue cartesian_waypoints on HBM-resident buffers (raw device addresses); returns immediately -- the
+        caller synchronises the stream.  The per-path state of the passes and, without d_goals, the poses are kept in
+        scratch of the handle's slot."""
+        self._env_options()
+        if P < 0 or S < 1 or W < S:
+            raise ValueError(f"{P} paths of {S} targets in {W} rows: expected P >= 0 and W >= S >= 1")
+        self._chk(self._L.pikamd_cartesian_waypoints_device(
+            self._h, C.byref(params), C.byref(cartesian), P, S, W, d_start or None, d_targets or None,
+            d_n_targets or None, d_max_joint_step or None, d_solution or None, d_status or None, d_cost or None,
+            d_stats or None, d_reached or None, d_steps or None, d_segment_steps or None, d_fraction or None,
+            d_goals or None, stream or None, slot))
+
+    def cartesian_waypoints_kernel_name(self, params: Params, P: int) -> str:
+        """the kernel that walks the segments of P paths of cartesian_waypoints (pikamd_cartesian_waypoints_kernel_name)"""
+        self._env_options()
+        return self._L.pikamd_cartesian_waypoints_kernel_name(self._h, C.byref(params), P).decode()
 
     # ---- Cartesian paths from a pose: the start state restarted until the path holds -------
     def search_paths(self, params: Params, goals, seed, max_attempts: int, max_joint_step=None, rng_seed: int = 0,
