@@ -504,6 +504,10 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
  *     if p->return_approximate_solution and a gate is set and st > 0 and not pass(sol, seed[b]):
  *       st = PIKAMD_GATE_REFUSED; sol = seed[b]     (the approximate-solution gate below, :263-266; cost and stats stay
  *                                                    what the solve returned, as for a refused path jump)
+ *     if a model is set and st > 0 and not valid(sol):  st = PIKAMD_VALIDITY_REFUSED; sol = seed[b]
+ *                                                   (the validity model below, in the solution callback's place, :269-274;
+ *                                                    cost and stats stay what the solve returned; no cost_fn invocation
+ *                                                    is counted)
  *     solution[b] = sol; status[b] = st; final_cost[b] = cost; stats[b] += stats (field by field); attempts[b] = a + 1
  *     if st > 0: b is closed        (PIKAMD_SUCCESS or PIKAMD_APPROXIMATE: error_code SUCCESS ends the reference's loop)
  *     else: init[b] = draw(b, a + 1, init[b])
@@ -517,17 +521,21 @@ const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params*
  *     attempt's start, as in the reference.
  *
  * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch (with a gate:
- * pikamd_solve_batch + pikamd_gate_batch).  With return_approximate_solution set and NO gate on the handle, attempt 0
- * always closes a problem (attempts == 1 everywhere); with a gate the restarts run for every refused answer.  A batch cut into
+ * pikamd_solve_batch + pikamd_gate_batch; with a model: + pikamd_validity_batch).  With return_approximate_solution set
+ * and neither a gate nor a model on the handle, attempt 0 always closes a problem (attempts == 1 everywhere); with a
+ * gate or a model the restarts run for every refused answer.  A batch cut into
  * calls or shards with matching problem_offset gives the answers of one call.  The attempts of one problem are
  * independent computations, so the library may run them one after the other or side by side (option
  * search_schedule = adaptive | sequential | parallel: like the other scheduling options it changes no result).
  * all_solution / all_status: when either is given EVERY attempt of every problem is run and recorded, without an
  * early exit -- the rows behind a problem's winner are real results (several distinct IK solutions per target, for
- * a caller who collision-checks them); row a is what one pikamd_solve_batch from start a returns, gated like the
- * loop's.  The primary outputs are the loop's whether or not all_* is given.
+ * a caller who collision-checks them); row a is what one pikamd_solve_batch from start a returns, gated and tested
+ * like the loop's.  The primary outputs are the loop's whether or not all_* is given.
  * The approximate-solution gate (src/pick_ik_plugin.cpp:219-267) is the handle's (pikamd_set_approximate_gate below;
- * none by default); the solution callback stays with the caller.
+ * none by default).  The solution callback (:269-274) is host code and stays with the caller; the validity model of the
+ * handle (pikamd_set_validity_model below; none by default) stands in its place, applied whenever the handle has one,
+ * independent of return_approximate_solution.  A call that the fast kernels serve (option arithmetic = fast) is refused
+ * with PIKAMD_EUNSUPPORTED while a model is set: the test's arithmetic is the exact flavour's.
  * GLOBAL mode (mode 0) is refused here: pikamd_search_global_batch serves it.
  *   goal_pos_quat [B][n_tips][7], seed [B][dof], initial_guess [B][dof] (NULL = seed), solution [B][dof], status [B],
  *   final_cost [B] (may be NULL), stats [B] (may be NULL), attempts [B] (may be NULL),
@@ -569,6 +577,7 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
  *                                with rng_seed_a = rng_seed + ((uint64_t)a << 32)      (mod 2^64)
  *     if p->return_approximate_solution and a gate is set and st > 0 and not pass(sol, seed[b]):
  *       st = PIKAMD_GATE_REFUSED; sol = seed[b]                  (as in pikamd_search_batch; cost and stats stay)
+ *     if a model is set and st > 0 and not valid(sol):  st = PIKAMD_VALIDITY_REFUSED; sol = seed[b]          (likewise)
  *     solution[b] = sol; status[b] = st; final_cost[b] = cost; stats[b] += stats (field by field); attempts[b] = a + 1
  *     if st > 0: b is closed     else: init[b] = draw(b, a + 1, init[b])
  *
@@ -579,15 +588,18 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
  * word gives every attempt INIT / REPRODUCE streams of its own for all problem indices below 2^32; a = 0 is the
  * caller's seed unchanged.
  *
- * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch.  With
- * return_approximate_solution set and no gate on the handle, every problem closes at attempt 0.  A batch cut into calls or shards with matching
+ * Consequences: max_attempts = 1 with a valid initial guess is exactly pikamd_solve_batch (with a gate: +
+ * pikamd_gate_batch; with a model: + pikamd_validity_batch).  With return_approximate_solution set and neither a gate
+ * nor a model on the handle, every problem closes at attempt 0.  A batch cut into calls or shards with matching
  * problem_offset gives the answers of one call.  A restart starts from the re-drawn state, as the plugin shim's loop
  * does (the reference re-randomises init_state but keeps passing ik_seed_state; seed[b] stays the displacement
  * reference and what a failure returns).  The approximate-solution gate is the handle's
- * (pikamd_set_approximate_gate); the solution callback stays with the caller.
+ * (pikamd_set_approximate_gate); the solution callback stays with the caller, and the handle's validity model
+ * (pikamd_set_validity_model) stands in its place -- for every kernel flavour: the test is a kernel of its own between
+ * an attempt and its fold.
  * all_solution [B][max_attempts][dof] / all_status [B][max_attempts]: when either is given EVERY attempt of every
  * problem runs, without an early exit; row a is what the one-record solve above returns from the start the loop's
- * draws give attempt a (every attempt counted as failed) with rng_seed_a, gated like the loop's.  The primary outputs
+ * draws give attempt a (every attempt counted as failed) with rng_seed_a, gated and tested like the loop's.  The primary outputs
  * are the loop's either way.
  * Accepts what pikamd_solve_batch accepts in global mode: every kernel flavour, species, several tip frames,
  * floating and mimic chains, unbounded variables.  max_attempts is 1..PIKAMD_MAX_ATTEMPTS; B = 0 returns 0; NULL is
@@ -633,7 +645,8 @@ int32_t pikamd_search_global_batch_device(pikamd_solver* s, const pikamd_params*
  * A failed attempt is not evaluated.  NULL = no gate, the default: every result is what it was.  Like
  * pikamd_set_option: not concurrent with another call on the handle, read when a call is made.
  * pikamd_solve_batch*, pikamd_solve_paths* and pikamd_solve_batch_host IGNORE the gate: they are the solver, the gate
- * belongs to the loop around it. */
+ * belongs to the loop around it.  They ignore a validity model (pikamd_set_validity_model) in the same way, and so does
+ * every path entry point. */
 typedef struct pikamd_gate {
     double cost_threshold;  /* approximate_solution_cost_threshold; <= 0: no goal is tested (:240-242) */
     double joint_threshold; /* approximate_solution_joint_threshold; not > 0: no limit (:253) */
@@ -940,6 +953,61 @@ int32_t pikamd_cartesian_waypoints_device(pikamd_solver* s, const pikamd_params*
                                           int32_t* d_reached, int32_t* d_steps, int32_t* d_segment_steps,
                                           double* d_fraction, double* d_goals, void* stream, int32_t slot);
 const char* pikamd_cartesian_waypoints_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P);
+/* ---- Sphere collision model: the validity test of a handle -------------------------------------------
+ * Behind every solve searchPositionIK calls the solution callback (src/pick_ik_plugin.cpp:269-274), in MoveIt the
+ * state-validity check: an answer it refuses becomes a failure and the search restarts from a random state.  A host
+ * callback cannot run inside a device search; what can is the test GPU planners use: the robot as spheres fixed to
+ * its links, obstacles as spheres fixed in the base frame, and a list of sphere pairs that must not overlap.
+ *
+ * pikamd_validity_batch: valid[i] / clearance[i] / centres[i] of candidate q[i], DEFINED by entry points above:
+ *   centre_k(q):  after_variable = -1: centres[k] as given (copied, no arithmetic)
+ *                 after_variable = v:  the position (first three numbers) of pikamd_fk_batch of a handle made by
+ *                                      pikamd_create IN THE SAME LIBRARY, arithmetic = exact, for the chain cut behind
+ *                                      variable v: dof = v + 1, the first v + 1 entries of every per-variable array,
+ *                                      tip_xyz_rpy = (centre, 0, 0, 0), evaluated at q[0..v]
+ *   for pair m = (i, j), ascending m:  dx, dy, dz = centre_i - centre_j by component
+ *                                      d2 = (dx*dx + dy*dy) + dz*dz;  clear_m = sqrt(d2) - (r_i + r_j)
+ *                                      (every operation rounded on its own, IEEE square root, in every flavour)
+ *   clearance = +infinity;  for m ascending: if clear_m < clearance: clearance = clear_m      (a NaN never replaces)
+ *   valid = 0 if clear_m < 0.0 for some m, else 1                                        (a NaN does not trip the test)
+ * Touching spheres (clear_m = 0.0) are valid.  n_pairs = 0 gives valid = 1 and clearance = +infinity everywhere.  The
+ * same arithmetic serves every handle, whatever its option `arithmetic` (as the restart draws do).
+ *   q [n][dof], valid [n], clearance [n] (may be NULL), centres [n][n_spheres][3] (may be NULL; caller's sphere order).
+ * Without a model on the handle: PIKAMD_EINVAL.  n = 0 returns 0.  Not with the option joint_layout = soa.
+ *
+ * pikamd_set_validity_model: the model of this handle (NULL: none, the default); like pikamd_set_option not concurrent
+ * with another call on the handle, read when a call is made.  It copies the model, uploads it and synchronises.
+ * PIKAMD_EINVAL: a NULL array that is needed, counts outside 0..PIKAMD_MAX_SPHERES / 0..PIKAMD_MAX_SPHERE_PAIRS, a
+ * radius or centre that is not finite, a radius below 0, a pair index out of range or i == j, after_variable outside
+ * -1..dof-1 or naming the _X / _Y slot of a planar joint (the chain cannot be cut there).  PIKAMD_EUNSUPPORTED: a
+ * handle with several tip frames, with a floating joint, or with mimic joints.
+ *
+ * The model is the validity step of pikamd_search_batch* and pikamd_search_global_batch* (their loops above), applied
+ * to PIKAMD_SUCCESS as well as PIKAMD_APPROXIMATE, behind the gate; a failed or gate-refused attempt is not tested.
+ * pikamd_solve_batch*, pikamd_solve_batch_host and every path entry point (pikamd_solve_paths*, pikamd_search_paths*,
+ * pikamd_search_global_paths*, pikamd_cartesian_paths*, pikamd_cartesian_waypoints*) IGNORE it. */
+#define PIKAMD_MAX_SPHERES 32
+#define PIKAMD_MAX_SPHERE_PAIRS 256
+#define PIKAMD_VALIDITY_REFUSED (-1004) /* outside MoveItErrorCodes, like PIKAMD_GATE_REFUSED */
+typedef struct pikamd_sphere {
+    int32_t after_variable; /* the sphere is fixed to the link behind the joint of this variable; -1: fixed in the base frame (an obstacle, the base link) */
+    int32_t reserved;       /* 0 */
+    double centre[3];       /* in that link's frame (after_variable = -1: in the base frame) */
+    double radius;
+} pikamd_sphere;
+typedef struct pikamd_validity_model {
+    int32_t n_spheres;
+    const pikamd_sphere* spheres;
+    int32_t n_pairs;
+    const int32_t* pairs; /* [n_pairs][2] sphere indices that must not overlap */
+} pikamd_validity_model;
+int32_t pikamd_set_validity_model(pikamd_solver* s, const pikamd_validity_model* m);
+/* host pointers; synchronous */
+int32_t pikamd_validity_batch(pikamd_solver* s, int64_t n, const double* q, int32_t* valid, double* clearance,
+                              double* centres);
+/* device pointers; enqueues on `stream` and returns without synchronising */
+int32_t pikamd_validity_batch_device(pikamd_solver* s, int64_t n, const double* d_q, int32_t* d_valid,
+                                     double* d_clearance, double* d_centres, void* stream);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -27,6 +27,7 @@
 #include "pik_solver.hpp"
 #include "pik_startpath_ops.hpp"
 #include "pik_urdf.hpp"
+#include "pik_validity_ops.hpp"
 
 namespace pik {
 char* error_buffer() {
@@ -54,6 +55,7 @@ PIK_DECLARE_OPS_FAMILY(void, startpath)
 PIK_DECLARE_OPS_FAMILY(void, globalpath)
 PIK_DECLARE_OPS_FAMILY(void, cartesian)
 PIK_DECLARE_OPS_FAMILY(void, polyline)
+PIK_DECLARE_OPS_FAMILY(void, validity)
 } // namespace pik_exact
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
@@ -89,7 +91,7 @@ enum Flavour {
 #endif
     N_FLAVOURS
 };
-enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, FAM_POLYLINE, N_FAMILIES };
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, FAM_POLYLINE, FAM_VALIDITY, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -122,6 +124,13 @@ struct SolverExt : pikamd_solver {
     // pikamd_cartesian_waypoints*: per slot the per-path state of the passes and, for a call whose caller keeps none,
     // the interpolated poses
     pik::DevBuf polyline_rows[pik::N_SLOTS];
+    // pikamd_set_validity_model: the sphere model as the kernels read it, its device image (the chain's constants in
+    // the exact flavour's layout + the model: pik_validity_ops.hpp) and, from pikamd_create, the variables that are
+    // the _X / _Y slot of a planar joint (no chain can be cut behind them)
+    bool validity_set = false;
+    pik::ValidityModelK validity_model;
+    pik::DevBuf validity_dev;
+    uint32_t planar_xy_mask = 0;
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -146,12 +155,16 @@ const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
 #endif
      untyped<pik::RestartOps, pik::restart_ops>, untyped<pik::StartPathOps, pik::startpath_ops>,
      untyped<pik::GlobalPathOps, pik::globalpath_ops>, untyped<pik::CartesianOps, pik::cartesian_ops>,
-     untyped<pik::PolylineOps, pik::polyline_ops>},
-#if !defined(PIK_STRICT)
+     untyped<pik::PolylineOps, pik::polyline_ops>,
+#if defined(PIK_STRICT)
+     untyped<pik::ValidityOps, pik::validity_ops>},
+#else
+     nullptr}, // (the sphere validity test is the exact flavour's for every handle: validity_ops_of)
     {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops,
-     pik_exact::startpath_ops, pik_exact::globalpath_ops, pik_exact::cartesian_ops, pik_exact::polyline_ops},
-    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr, nullptr},
-    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr, nullptr},
+     pik_exact::startpath_ops, pik_exact::globalpath_ops, pik_exact::cartesian_ops, pik_exact::polyline_ops,
+     pik_exact::validity_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr, nullptr, nullptr},
 #endif
 };
 // ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
@@ -336,6 +349,34 @@ int gate_for_call(pikamd_solver* s, const pik::ParamsK& pk, int slot, hipStream_
     return 0;
 }
 
+// The kernels of the sphere validity test: the exact flavour's in the product library, whatever serves the handle's
+// solves (the verification library: its own) -- one arithmetic for every handle.
+const pik::ValidityOps* validity_ops_of(const pikamd_solver* s) {
+#if defined(PIK_STRICT)
+    return ops_at<pik::ValidityOps>(FL_HOME, FAM_VALIDITY, s->chain.dof);
+#else
+    return ops_at<pik::ValidityOps>(FL_EXACT, FAM_VALIDITY, s->chain.dof);
+#endif
+}
+
+// what the test cannot walk: several tip frames, a floating joint, mimic joints (they may be set after the model)
+int validity_chain_ok(const pikamd_solver* s, const char* who) {
+    if (s->n_tips != 1) return fail(PIKAMD_EUNSUPPORTED, "%s: the validity model is for handles with one tip frame", who);
+    if ((s->chain.float_mask | s->chain.skip_mask) != 0u)
+        return fail(PIKAMD_EUNSUPPORTED, "%s: the validity model does not know floating joints", who);
+    if (s->chain.n_mimic != 0) return fail(PIKAMD_EUNSUPPORTED, "%s: the validity model does not know mimic joints", who);
+    return 0;
+}
+
+// The validity step of a global-mode search call: the handle's model, or null ops where it has none.
+int validity_for_call(pikamd_solver* s, const char* who, const pik::ValidityOps** ops) {
+    *ops = nullptr;
+    if (!ext_of(s)->validity_set) return 0;
+    if (int rc = validity_chain_ok(s, who)) return rc;
+    *ops = validity_ops_of(s);
+    return *ops ? 0 : no_kernels(s->chain.dof);
+}
+
 } // namespace
 
 extern "C" {
@@ -413,7 +454,11 @@ int32_t pikamd_create(const pikamd_chain* chain, int32_t device_ordinal, pikamd_
     *out = nullptr;
     pik::ChainHost ch;
     if (const char* msg = pik::build_chain(chain, ch)) return fail(PIKAMD_EINVAL, "%s", msg);
-    return create_solver(&ch, 1, device_ordinal, out);
+    if (int rc = create_solver(&ch, 1, device_ordinal, out)) return rc;
+    for (int j = 0; chain->joint_type && j < chain->dof; ++j)
+        if (chain->joint_type[j] == PIKAMD_JOINT_PLANAR_X || chain->joint_type[j] == PIKAMD_JOINT_PLANAR_Y)
+            ext_of(*out)->planar_xy_mask |= 1u << j;
+    return 0;
 }
 
 int32_t pikamd_create_multi(const pikamd_multi_chain* chain, int32_t device_ordinal,
@@ -531,6 +576,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : ext_of(s)->polyline_rows) b.release();
     for (auto& b : ext_of(s)->globalpath_rows) b.release();
     ext_of(s)->gate_params_dev.release();
+    ext_of(s)->validity_dev.release();
     for (auto& j : s->jobs) {
         j.dev.release();
         j.host.release();
@@ -1850,6 +1896,20 @@ int search_gate(pikamd_solver* s, const pik::ParamsK& pk, int slot, hipStream_t 
     return gate_for_call(s, pk, slot, st, &a.gate, &a.gate_joint, &a.gate_params);
 }
 
+// The handle's sphere model into the arguments of a local-mode call: the test runs inside the exact flavours' search
+// kernels (pik_search.hpp search_attempt), whose chain constants are the ones the model's image was packed with.  A
+// call the fast kernels serve has no such step: refused while a model is set.
+int search_validity(pikamd_solver* s, const pikamd_params* p, pik::SearchArgs* a) {
+    if (!ext_of(s)->validity_set) return 0;
+    if (!is_exact(flavour_of(s, p, nullptr)))
+        return fail(PIKAMD_EUNSUPPORTED,
+                    "pikamd_search_batch: a validity model is set and the option arithmetic = fast has the fast kernels "
+                    "serve this call; they have no validity step (arithmetic = exact, or pikamd_set_validity_model(s, NULL))");
+    if (int rc = validity_chain_ok(s, "pikamd_search_batch")) return rc;
+    if (a) a->validity = ext_of(s)->validity_dev.p;
+    return 0;
+}
+
 // ... and of a global-mode one (goal and seed apart: they go to the solver)
 pik::RestartArgs restart_args(int64_t B, int32_t K, const SearchArrays& d, uint64_t rng_seed, int64_t problem_offset) {
     pik::RestartArgs r = {};
@@ -1886,10 +1946,12 @@ int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::SearchOps* ops = search_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
+    if (int rc = search_validity(s, p, nullptr)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     pik::SearchArgs a;
     if (int rc = search_args(s, p, slot, B, max_attempts, d, rng_seed, problem_offset, a)) return rc;
     if (int rc = search_gate(s, pk, slot, (hipStream_t)stream, a)) return rc;
+    if (int rc = search_validity(s, p, &a)) return rc;
     return ops->solve(s, pk, a, (hipStream_t)stream, slot);
 }
 
@@ -1904,6 +1966,7 @@ int32_t pikamd_search_batch(pikamd_solver* s, const pikamd_params* p, int64_t B,
     if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
     const pik::SearchOps* ops = search_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
+    if (int rc = search_validity(s, p, nullptr)) return rc;
     Staging st(s, SEARCH.name);
     if (int rc = st.begin()) return rc;
     SearchArrays d;
@@ -1911,6 +1974,7 @@ int32_t pikamd_search_batch(pikamd_solver* s, const pikamd_params* p, int64_t B,
     pik::SearchArgs a;
     if (int rc = search_args(s, p, Staging::SLOT, B, max_attempts, d, rng_seed, problem_offset, a)) return rc;
     if (int rc = search_gate(s, pk, Staging::SLOT, st.stream(), a)) return rc;
+    if (int rc = search_validity(s, p, &a)) return rc;
     if (int rc = st.upload()) return rc;
     return st.finish(ops->solve(s, pk, a, st.stream(), Staging::SLOT));
 }
@@ -1957,6 +2021,10 @@ int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::Param
     r.goal = d_goal;
     r.seed = d_seed;
     if (int rc = gate_for_call(s, pk, slot, stream, &r.gate, &r.gate_joint, &r.gate_params)) return rc;
+    // the validity step behind the gate: the rows kernel of the sphere model, where the handle has one
+    const pik::ValidityOps* vops = nullptr;
+    if (int rc = validity_for_call(s, "pikamd_search_global_batch", &vops)) return rc;
+    pik::ValidityRows vr = {r.B, r.every, 0, r.open, r.row_solution, r.row_status, d_seed};
     pik::BatchRecord rec;
     std::memset(&rec, 0, sizeof rec);
     rec.B = r.B;
@@ -1992,6 +2060,9 @@ int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::Param
         r.last = (a == r.K - 1) ? 1 : 0;
         if (r.gate)
             if (int rc = ops->gate(s, pk, r, stream, slot)) return give_up(rc);
+        if (vops)
+            if (int rc = vops->rows(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, vr, stream))
+                return give_up(rc);
         if (int rc = ops->fold(s, pk, r, stream, slot)) return give_up(rc);
         if (sync_between && !r.last) {
             unsigned cnt = 0;
@@ -2547,6 +2618,118 @@ int32_t pikamd_set_approximate_gate(pikamd_solver* s, const pikamd_gate* gate) {
     SolverExt* x = ext_of(s);
     x->gate_set = gate != nullptr;
     if (gate) x->gate = *gate;
+    return 0;
+}
+
+// ---- the sphere validity model (the solution callback's place, src/pick_ik_plugin.cpp:269-274) -------
+int32_t pikamd_set_validity_model(pikamd_solver* s, const pikamd_validity_model* m) {
+    if (int rc = check_solver(s)) return rc;
+    SolverExt* x = ext_of(s);
+    if (!m) {
+        x->validity_set = false;
+        return 0;
+    }
+    const char* who = "pikamd_set_validity_model";
+    if (m->n_spheres < 0 || m->n_spheres > PIKAMD_MAX_SPHERES)
+        return fail(PIKAMD_EINVAL, "%s: n_spheres %d: expected 0..%d", who, (int)m->n_spheres, PIKAMD_MAX_SPHERES);
+    if (m->n_pairs < 0 || m->n_pairs > PIKAMD_MAX_SPHERE_PAIRS)
+        return fail(PIKAMD_EINVAL, "%s: n_pairs %d: expected 0..%d", who, (int)m->n_pairs, PIKAMD_MAX_SPHERE_PAIRS);
+    if ((m->n_spheres > 0 && !m->spheres) || (m->n_pairs > 0 && !m->pairs))
+        return fail(PIKAMD_EINVAL, "%s: spheres / pairs must not be NULL", who);
+    if (int rc = validity_chain_ok(s, who)) return rc;
+    const int dof = s->chain.dof;
+    for (int k = 0; k < m->n_spheres; ++k) {
+        const pikamd_sphere& sp = m->spheres[k];
+        if (!(std::isfinite(sp.radius) && sp.radius >= 0.0 && std::isfinite(sp.centre[0]) && std::isfinite(sp.centre[1]) &&
+              std::isfinite(sp.centre[2])))
+            return fail(PIKAMD_EINVAL, "%s: sphere %d: centre and radius must be finite, the radius not below 0", who, k);
+        if (sp.after_variable < -1 || sp.after_variable >= dof)
+            return fail(PIKAMD_EINVAL, "%s: sphere %d: after_variable %d: expected -1..%d", who, k, (int)sp.after_variable, dof - 1);
+        if (sp.after_variable >= 0 && ((x->planar_xy_mask >> sp.after_variable) & 1u))
+            return fail(PIKAMD_EINVAL, "%s: sphere %d: after_variable %d is the x or y slot of a planar joint (name its theta)",
+                        who, k, (int)sp.after_variable);
+    }
+    for (int p = 0; p < m->n_pairs; ++p) {
+        const int a = m->pairs[2 * p], b = m->pairs[2 * p + 1];
+        if (a < 0 || a >= m->n_spheres || b < 0 || b >= m->n_spheres || a == b)
+            return fail(PIKAMD_EINVAL, "%s: pair %d = (%d, %d): two different spheres of 0..%d expected", who, p, a, b,
+                        (int)m->n_spheres - 1);
+    }
+    const pik::ValidityOps* ops = validity_ops_of(s);
+    if (!ops) return no_kernels(dof);
+    // the kernels' copy: the spheres in chain order (stable), the caller's numbering kept beside them
+    pik::ValidityModelK k;
+    std::memset(&k, 0, sizeof k);
+    k.n_spheres = m->n_spheres;
+    k.n_pairs = m->n_pairs;
+    int n = 0;
+    for (int v = -1; v < dof; ++v)
+        for (int i = 0; i < m->n_spheres; ++i) {
+            const pikamd_sphere& sp = m->spheres[i];
+            if (sp.after_variable != v) continue;
+            k.after[n] = v;
+            k.index[n] = i;
+            for (int c = 0; c < 3; ++c) k.centre[n][c] = sp.centre[c];
+            if (sp.centre[0] == 0.0 && sp.centre[1] == 0.0 && sp.centre[2] == 0.0) k.zero_mask |= 1u << n;
+            ++n;
+        }
+    for (int i = 0; i < m->n_spheres; ++i) k.radius[i] = m->spheres[i].radius;
+    for (int p = 0; p < 2 * m->n_pairs; ++p) k.pairs[p / 2][p % 2] = m->pairs[p];
+    std::vector<char> image(ops->image_bytes);
+    ops->pack(s, k, image.data());
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize()); // (no kernel in flight reads the image that is rewritten)
+    x->validity_set = false;
+    if (int rc = x->validity_dev.ensure(image.size())) return rc;
+    HIP_TRY(hipMemcpy(x->validity_dev.p, image.data(), image.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    x->validity_model = k;
+    x->validity_set = true;
+    return 0;
+}
+
+// what both validity entry points refuse
+static int check_validity_call(pikamd_solver* s, int64_t n, const void* q, const void* valid, const pik::ValidityOps** ops) {
+    if (int rc = check_solver(s)) return rc;
+    const char* who = "pikamd_validity_batch";
+    if (!ext_of(s)->validity_set) return fail(PIKAMD_EINVAL, "%s: the handle has no validity model (pikamd_set_validity_model)", who);
+    if (n < 0) return fail(PIKAMD_EINVAL, "%s: n = %lld: expected n >= 0", who, (long long)n);
+    if (n > 0 && (!q || !valid)) return fail(PIKAMD_EINVAL, "%s: q and valid must not be NULL", who);
+    if (s->opt.soa) return fail(PIKAMD_EINVAL, "joint_layout soa: not with %s (its arrays are [n][dof])", who);
+    if (int rc = validity_chain_ok(s, who)) return rc;
+    *ops = validity_ops_of(s);
+    return *ops ? 0 : no_kernels(s->chain.dof);
+}
+
+int32_t pikamd_validity_batch_device(pikamd_solver* s, int64_t n, const double* d_q, int32_t* d_valid,
+                                     double* d_clearance, double* d_centres, void* stream) {
+    const pik::ValidityOps* ops = nullptr;
+    if (int rc = check_validity_call(s, n, d_q, d_valid, &ops)) return rc;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(s->device));
+    return ops->check(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, n, d_q, d_valid, d_clearance,
+                      d_centres, (hipStream_t)stream);
+}
+
+int32_t pikamd_validity_batch(pikamd_solver* s, int64_t n, const double* q, int32_t* valid, double* clearance,
+                              double* centres) {
+    const pik::ValidityOps* ops = nullptr;
+    if (int rc = check_validity_call(s, n, q, valid, &ops)) return rc;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t d = (size_t)s->chain.dof, N = (size_t)n, n3 = 3 * (size_t)ext_of(s)->validity_model.n_spheres;
+    const size_t sz[4] = {sizeof(double) * d * N, sizeof(int32_t) * N, sizeof(double) * N, sizeof(double) * n3 * N};
+    for (int i = 0; i < 4; ++i)
+        if (int rc = s->stage[i].ensure(sz[i])) return rc;
+    HIP_TRY(hipMemcpy(s->stage[0].p, q, sz[0], hipMemcpyHostToDevice));
+    if (int rc = pikamd_validity_batch_device(s, n, (const double*)s->stage[0].p, (int32_t*)s->stage[1].p,
+                                              clearance ? (double*)s->stage[2].p : nullptr,
+                                              (centres && n3) ? (double*)s->stage[3].p : nullptr, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(valid, s->stage[1].p, sz[1], hipMemcpyDeviceToHost));
+    if (clearance) HIP_TRY(hipMemcpy(clearance, s->stage[2].p, sz[2], hipMemcpyDeviceToHost));
+    if (centres && n3) HIP_TRY(hipMemcpy(centres, s->stage[3].p, sz[3], hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
 

@@ -30,11 +30,28 @@
 
 #include "pik_path.hpp"
 #include "pik_search_ops.hpp"
+#if defined(PIK_STRICT)
+#include "pik_validity.hpp"
+#endif
 
 namespace pik {
 
 constexpr uint32_t STREAM_RESTART = 3u; // (streams 1 and 2: pik_math.hpp)
 constexpr int PIKAMD_GATE_REFUSED_K = -1002; // PIKAMD_GATE_REFUSED
+
+#if defined(PIK_STRICT)
+// The validity step of an attempt (src/pick_ik_plugin.cpp:269-274, the solution callback's place): the sphere test of
+// pik_validity.hpp on the attempt's answer.  A real call with the lane's centres in private memory (96 doubles at the
+// most, indexed by sphere): the descents around it keep their registers, and a call without a model never gets here.
+template <int D>
+__device__ __noinline__ bool search_valid(CK<D> c_in, const void* image, const double (&q)[D]) {
+    CK<D> c = scalar_ref(c_in);
+    VM m = scalar_ref(((const PIK_CONSTANT ValidityImage<D>*)image)->model);
+    double store[3 * VALIDITY_MAX_SPHERES];
+    double clearance;
+    return validity_clear<D>(c, m, q, store, 1, clearance);
+}
+#endif
 
 // (hi - lo) * u + lo with every operation rounded on its own, whatever contraction the flavour is compiled with
 // (the fast flavour's uniform_real is one fused expression): the restart states are the same doubles in all flavours
@@ -163,6 +180,15 @@ __device__ __forceinline__ void search_attempt(CK<D> c, PK p, const SearchArgs& 
             status = pass ? status : PIKAMD_GATE_REFUSED_K;
         }
     }
+#if defined(PIK_STRICT)
+    // The validity step, behind the gate and whether or not the call is gated: an answer the handle's sphere model
+    // refuses is PIKAMD_VALIDITY_REFUSED and the seed -- the row, the primary outputs, whether the problem stays open
+    // and search_finalize_kernel's winner use the tested status; cost and counters stay, no evaluation is counted.
+    if (a.validity != nullptr && __any(run && status > 0)) {
+        const bool ok = search_valid<D>(c, a.validity, s.best);
+        status = (status > 0 && !ok) ? PIKAMD_VALIDITY_REFUSED_K : status;
+    }
+#endif
     StatsK st;
     st.cost_evals = (s.found == 2) ? 0 : 1 + (long long)s.steps * (2 * D + 3);
     st.generations = s.iters;

@@ -40,6 +40,10 @@ struct SearchArgs {
     int gate;                     // 0: no gate (the fields below are not read)
     double gate_joint;            // approximate_solution_joint_threshold (not > 0: no limit)
     const ParamsK* gate_params;
+    // The sphere validity model of the handle (pikamd_set_validity_model), applied behind the gate: the device image
+    // of pik_validity_ops.hpp, or null -- no model, and always null in a call of the path-from-pose families.  Read by
+    // the exact flavours' kernels only (the host refuses a model on a call the fast kernels serve).
+    const void* validity;
 };
 
 // p' of pikamd_gate_batch, from the call's converted parameters: the gate's cost threshold in place of the call's when

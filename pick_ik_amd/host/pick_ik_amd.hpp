@@ -791,6 +791,32 @@ class Solver {
         if (pikamd_set_approximate_gate(h_, nullptr) != 0) throw std::runtime_error(pikamd_last_error());
     }
 
+    // The sphere validity model (pikamd_set_validity_model), in the place of the reference's solution callback
+    // (src/pick_ik_plugin.cpp:269-274): spheres fixed to links or to the base frame, pairs (2 indices each) that must
+    // not overlap.  While a model is set the two *_search_batch calls above test every answer behind the gate -- a
+    // refused answer is PIKAMD_VALIDITY_REFUSED and the seed, and the search restarts; clear_validity_model: none.
+    void set_validity_model(const std::vector<pikamd_sphere>& spheres, const std::vector<int32_t>& pairs) {
+        if (pairs.size() % 2 != 0) throw std::invalid_argument("pick_ik_amd: pairs holds two sphere indices per pair");
+        const pikamd_validity_model m = {static_cast<int32_t>(spheres.size()), spheres.data(),
+                                         static_cast<int32_t>(pairs.size() / 2), pairs.data()};
+        if (pikamd_set_validity_model(h_, &m) != 0) throw std::runtime_error(pikamd_last_error());
+        n_spheres_ = static_cast<int>(spheres.size());
+    }
+    void clear_validity_model() {
+        if (pikamd_set_validity_model(h_, nullptr) != 0) throw std::runtime_error(pikamd_last_error());
+        n_spheres_ = 0;
+    }
+    // pikamd_validity_batch for one candidate: is `q` valid; *clearance (may be null): the smallest distance between
+    // the surfaces of a pair; *centres (may be null): the sphere centres in the base frame, 3 numbers per sphere
+    bool validity(const std::vector<double>& q, double* clearance = nullptr, std::vector<double>* centres = nullptr) const {
+        check_size(q);
+        int32_t valid = 0;
+        if (centres) centres->assign(3 * static_cast<size_t>(n_spheres_), 0.0);
+        if (pikamd_validity_batch(h_, 1, q.data(), &valid, clearance, centres ? centres->data() : nullptr) != 0)
+            throw std::runtime_error(pikamd_last_error());
+        return valid != 0;
+    }
+
     pikamd_solver* handle() const { return h_; }
 
     // pikamd_self_test: every kernel variant against the one-lane kernel on n generated targets of this
@@ -948,6 +974,7 @@ class Solver {
 
     int dof_;
     int n_tips_ = 1;
+    int n_spheres_ = 0; // of the validity model set through this object
     pikamd_solver* h_ = nullptr;
     Robot robot_;
     mutable CallRecord last_call_;

@@ -201,6 +201,46 @@ def panda() -> Chain:
 PANDA_HOME = np.array([0.0, -PI / 4, 0.0, -3.0 * PI / 4, 0.0, PI / 2, PI / 4])
 
 
+def cut_chain(ch: Chain, after_variable: int, centre=(0.0, 0.0, 0.0)) -> Chain:
+    """`ch` cut behind variable `after_variable`, with the point `centre` of that link's frame as its tip: the chain
+    whose forward kinematics DEFINES the centre of a sphere of a validity model (include/pick_ik_amd.h)."""
+    n = int(after_variable) + 1
+    return dataclasses.replace(
+        ch, name=f"{ch.name}_cut{n}", origin_xyz_rpy=np.ascontiguousarray(ch.origin_xyz_rpy[:n]),
+        axis=np.ascontiguousarray(ch.axis[:n]), joint_type=np.ascontiguousarray(ch.joint_type[:n]),
+        tip_xyz_rpy=np.array([centre[0], centre[1], centre[2], 0.0, 0.0, 0.0], dtype=np.float64),
+        qmin=np.ascontiguousarray(ch.qmin[:n]), qmax=np.ascontiguousarray(ch.qmax[:n]),
+        vmax=np.ascontiguousarray(ch.vmax[:n]), bounded=np.ascontiguousarray(ch.bounded[:n]), mimic=())
+
+
+#: obstacles of panda_spheres(): (centre in the base frame, radius) -- a post beside the arm, a shelf edge in front of
+#: it and a lamp above the workspace
+PANDA_OBSTACLES = (((0.25, 0.3, 0.6), 0.2), ((0.45, -0.2, 0.45), 0.15), ((-0.1, -0.35, 0.7), 0.2))
+
+
+def panda_spheres(obstacles=PANDA_OBSTACLES):
+    """A coarse sphere model of the Panda for the validity test (Solver.set_validity_model): (spheres, pairs).  Synthetic,
+    eyeballed from the link lengths of panda(): one sphere on the base link, one per moving link, a second one on the
+    last link (the flange: its centre is the link frame's origin) and the obstacles, fixed in the base frame.
+    spheres: (after_variable, centre, radius); pairs: every two robot spheres whose links are not the same and not
+    neighbours, and every moving-link sphere against every obstacle."""
+    robot = [
+        (-1, (0.0, 0.0, 0.07), 0.12),      # link0
+        (0, (0.0, 0.0, -0.12), 0.09),      # link1
+        (1, (0.0, -0.06, 0.0), 0.09),      # link2
+        (2, (0.04, 0.0, -0.08), 0.09),     # link3
+        (3, (-0.05, 0.06, 0.0), 0.09),     # link4
+        (4, (0.0, 0.04, -0.18), 0.08),     # link5
+        (5, (0.05, 0.0, 0.0), 0.08),       # link6
+        (6, (0.0, 0.0, 0.14), 0.07),       # link7 + hand
+        (6, (0.0, 0.0, 0.0), 0.05),        # flange
+    ]
+    spheres = robot + [(-1, tuple(c), float(r)) for c, r in obstacles]
+    pairs = [(i, j) for i in range(len(robot)) for j in range(i + 1, len(robot)) if robot[j][0] - robot[i][0] >= 2]
+    pairs += [(i, len(robot) + k) for i in range(1, len(robot)) for k in range(len(obstacles))]
+    return spheres, np.array(pairs, dtype=np.int32).reshape(-1, 2)
+
+
 def ur5() -> Chain:
     """Universal Robots UR5 (classic universal_robot URDF), base_link -> ee_link."""
     origins = [

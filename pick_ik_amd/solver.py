@@ -106,6 +106,26 @@ class Gate(C.Structure):
 #: status of an answer the gate refused (PIKAMD_GATE_REFUSED)
 GATE_REFUSED = -1002
 
+
+class Sphere(C.Structure):
+    """pikamd_sphere: a sphere fixed to the link behind the joint of variable `after_variable` (-1: fixed in the base
+    frame -- an obstacle, the base link), its centre in that link's frame"""
+    _fields_ = [("after_variable", C.c_int32), ("reserved", C.c_int32), ("centre", C.c_double * 3), ("radius", C.c_double)]
+
+    def __init__(self, after_variable=-1, centre=(0.0, 0.0, 0.0), radius=0.0):
+        super().__init__(int(after_variable), 0, (C.c_double * 3)(*[float(v) for v in centre]), float(radius))
+
+
+class ValidityModel(C.Structure):
+    """pikamd_validity_model"""
+    _fields_ = [("n_spheres", C.c_int32), ("spheres", C.POINTER(Sphere)), ("n_pairs", C.c_int32), ("pairs", C.POINTER(C.c_int32))]
+
+
+#: limits of a validity model (PIKAMD_MAX_SPHERES, PIKAMD_MAX_SPHERE_PAIRS) and the status of an answer the validity
+#: test refused (PIKAMD_VALIDITY_REFUSED)
+MAX_SPHERES, MAX_SPHERE_PAIRS = 32, 256
+VALIDITY_REFUSED = -1004
+
 #: cartesian_paths: the first waypoint whose joint-space step is further than jump_factor times the mean step
 #: (PIKAMD_PATH_RELATIVE_JUMP)
 PATH_RELATIVE_JUMP = -1003
@@ -200,6 +220,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_search_global_paths", "pikamd_search_global_paths_device", "pikamd_search_global_paths_kernel_name",
     "pikamd_interpolate_poses", "pikamd_cartesian_paths", "pikamd_cartesian_paths_device", "pikamd_cartesian_kernel_name",
     "pikamd_cartesian_waypoints", "pikamd_cartesian_waypoints_device", "pikamd_cartesian_waypoints_kernel_name",
+    "pikamd_set_validity_model", "pikamd_validity_batch", "pikamd_validity_batch_device",
 )
 
 _libs = {}
@@ -305,6 +326,12 @@ def lib(strict: bool = False):
     L.pikamd_gate_batch.restype = C.c_int32
     L.pikamd_set_approximate_gate.argtypes = [vp, C.POINTER(Gate)]
     L.pikamd_set_approximate_gate.restype = C.c_int32
+    L.pikamd_set_validity_model.argtypes = [vp, C.POINTER(ValidityModel)]
+    L.pikamd_set_validity_model.restype = C.c_int32
+    L.pikamd_validity_batch.argtypes = [vp, C.c_int64, dp, ip, dp, dp]
+    L.pikamd_validity_batch.restype = C.c_int32
+    L.pikamd_validity_batch_device.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
+    L.pikamd_validity_batch_device.restype = C.c_int32
     L.pikamd_search_paths.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_uint64, C.c_int64,
                                       C.c_int32, dp, ip, dp, vp, ip, ip, vp]
     L.pikamd_search_paths.restype = C.c_int32
@@ -606,6 +633,40 @@ class Solver:
     def clear_approximate_gate(self) -> None:
         """no gate (the default): every result is what it was"""
         self._chk(self._L.pikamd_set_approximate_gate(self._h, None))
+
+    def set_validity_model(self, spheres, pairs) -> None:
+        """pikamd_set_validity_model: spheres = Sphere objects (or (after_variable, centre, radius) tuples), pairs =
+        [n_pairs][2] sphere indices that must not overlap.  The model is the validity step of search_global_batch
+        (a refused answer is VALIDITY_REFUSED and the search restarts) and what validity() tests."""
+        sph = [s if isinstance(s, Sphere) else Sphere(*s) for s in spheres]
+        arr = (Sphere * max(1, len(sph)))(*sph)
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        m = ValidityModel(len(sph), arr, pr.shape[0], pr.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._chk(self._L.pikamd_set_validity_model(self._h, C.byref(m)))
+        self._n_spheres = len(sph)
+
+    def clear_validity_model(self) -> None:
+        """no model (the default): every result is what it was"""
+        self._chk(self._L.pikamd_set_validity_model(self._h, None))
+        self._n_spheres = None
+
+    def validity(self, q, centres: bool = False):
+        """pikamd_validity_batch: (valid [n] bool, clearance [n]) of joint vectors q [n][dof]; centres=True: also the
+        sphere centres [n][n_spheres][3] in the base frame, in the model's order."""
+        q = _f64(q).reshape(-1, self.dof)
+        n = q.shape[0]
+        ns = getattr(self, "_n_spheres", None) or 0
+        valid = np.zeros(n, dtype=np.int32)
+        clearance = np.empty(n)
+        cen = np.empty((n, ns, 3)) if centres else None
+        self._chk(self._L.pikamd_validity_batch(self._h, n, _dp(q), _ip(valid), _dp(clearance),
+                                                _dp(cen) if centres else None))
+        return (valid != 0, clearance, cen) if centres else (valid != 0, clearance)
+
+    def validity_device(self, n: int, d_q: int, d_valid: int, d_clearance: int = 0, d_centres: int = 0, stream: int = 0):
+        """pikamd_validity_batch_device: device pointers, enqueued on `stream`"""
+        self._chk(self._L.pikamd_validity_batch_device(self._h, n, d_q, d_valid, d_clearance or None, d_centres or None,
+                                                       stream or None))
 
     def gd_step(self, params: Params, goal_pos_quat, seed, local, best, local_cost, best_cost):
         """One step() of src/ik_gradient.cpp:24-94 on n GradientIk states."""
