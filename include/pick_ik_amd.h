@@ -1008,6 +1008,51 @@ int32_t pikamd_validity_batch(pikamd_solver* s, int64_t n, const double* q, int3
 /* device pointers; enqueues on `stream` and returns without synchronising */
 int32_t pikamd_validity_batch_device(pikamd_solver* s, int64_t n, const double* d_q, int32_t* d_valid,
                                      double* d_clearance, double* d_centres, void* stream);
+/* ---- The validity model inside the path entry points that start from a joint state --------------------
+ * computeCartesianPath always receives a validity callback: it hands it to setFromIK for every waypoint, the first
+ * waypoint whose answer is in collision ends the path, the fraction counts the waypoints in front of it, and the
+ * relative jump test then runs over what is left.  pikamd_set_path_validity is the opt-in that puts the handle's
+ * sphere model (pikamd_set_validity_model above) in that place.
+ *
+ * With applies = (the switch is on and the handle has a model), the loop that defines pikamd_solve_paths (above)
+ * reads, for path p and waypoint k while held[p]:
+ *     (sol, st, cost, stats) = pikamd_solve_batch(local mode, goal[p][k], seed = initial guess = seed[p])
+ *     jump    = st > 0 and (the joint-step test, unchanged)
+ *     refused = applies and st > 0 and not jump and valid(sol) == 0
+ *                   (valid: pikamd_validity_batch's, bit for bit; a jumped answer is not tested; no cost_fn invocation
+ *                    is counted)
+ *     if st > 0 and not jump and not refused: hold, as before
+ *     else: solution[p][k] = seed[p]; status[p][k] = jump ? PIKAMD_PATH_JUMP : refused ? PIKAMD_VALIDITY_REFUSED : st;
+ *           held[p] = false
+ *     final_cost[p][k] = cost; stats[p][k] = stats      (what the call returned, also for a refused answer)
+ * With applies false this is the loop as it stands above: nothing changes.  The rows behind the refused one are blank
+ * as behind any other stop, and reached[p] counts the waypoints in front of it.
+ *
+ * pikamd_cartesian_paths is defined by pikamd_solve_paths per path and pikamd_cartesian_waypoints by
+ * pikamd_cartesian_paths per segment, so both inherit the step:
+ *   - pikamd_cartesian_paths: r counts the waypoints in front of the refused one, fraction = r / n, and the relative
+ *     test runs afterwards, over traj[0..r] of the cut path (MoveIt's order).  A cut changes the mean step, so the
+ *     relative stop can move, appear or vanish.
+ *   - pikamd_cartesian_waypoints: a refused row gives r_i < n_i; the path stops in that segment with
+ *     frac = i / S_p + (r_i / n_i) / S_p, and no later segment is started.  The relative test runs once, over the
+ *     stitched rows.
+ *   - The start state is not tested (MoveIt does not test it either).
+ * The test's arithmetic is the exact flavour's for every handle, as in pikamd_search_global_batch: a handle with
+ * arithmetic = fast is served (unlike pikamd_search_batch).  On the device the step is a pass of its own behind the
+ * walk (no walk kernel changes, no host round trip): the descents behind a collision are run and thrown away.
+ *
+ * pikamd_search_paths* and pikamd_search_global_paths* keep ignoring the model whatever the switch says: their
+ * attempt loops are fused with the walk.  pikamd_solve_batch* ignores it as before.
+ *
+ * pikamd_set_path_validity: 0 (the default) or 1; any other value is PIKAMD_EINVAL.  Like pikamd_set_approximate_gate
+ * not concurrent with another call on the handle, read when a call is made.  It needs no model: with the switch on and
+ * no model nothing changes, and pikamd_set_validity_model(s, NULL) leaves the switch as it is.  A handle the model
+ * cannot walk (several tip frames, a floating joint, mimic joints set after the model) is PIKAMD_EUNSUPPORTED at the
+ * path call.  A path call with reached = NULL keeps the count the step reads in the slot's scratch, which grows only
+ * when a call needs more. */
+/* 0 (default): the path entry points ignore the handle's validity model, as before.
+ * 1: pikamd_solve_paths*, pikamd_cartesian_paths*, pikamd_cartesian_waypoints* apply it (above). */
+int32_t pikamd_set_path_validity(pikamd_solver* s, int32_t on);
 /* ---- Device-side choice of the regime (option device_regime) -------------------------------------
  * A memetic call on one tip frame with one species and nothing forced (lanes_per_elite, its schedule, regime) is cut
  * into passes whose kernel variant is chosen when the pass starts: a one-wavefront router in front of the pass takes

@@ -85,13 +85,15 @@ FAMILIES = {
     "pik_polyline_inst.hip": (("fast", "exact"), ("strict",)),
     # the sphere validity test: ONE arithmetic for every handle (the exact flavour's; the verification library's own)
     "pik_validity_inst.hip": (("exact",), ("strict",)),
+    # the validity step of the path entry points (pikamd_set_path_validity): the same one arithmetic
+    "pik_pathvalid_inst.hip": (("exact",), ("strict",)),
 }
 #: the families behind the link list library_objects() gives (tests/test_build_cpu.py holds that list to the blocks it
 #: names, in their order): their objects are linked last, see link_objects()
 #: (in link order; tests/test_globalpath_cpu.py holds the memetic-start path objects to the end of the list, so a later
 #: family goes in front of them)
 APPENDED_FAMILIES = ("pik_startpath_inst.hip", "pik_cartesian_inst.hip", "pik_polyline_inst.hip", "pik_validity_inst.hip",
-                     "pik_globalpath_inst.hip")
+                     "pik_pathvalid_inst.hip", "pik_globalpath_inst.hip")
 
 
 def family_objects(family: str, flavour: str):
@@ -241,8 +243,8 @@ def _lib_stamp(strict: bool) -> str:
     # (+search: ... and the restart-search objects; +route: ... and, in the product library, the routed launcher's;
     #  +restart: ... and the restart launcher's; +startpath: ... and the start-search path kernels'; +globalpath: ... and the memetic-start path kernels';
     #  +cartesian: ... and the Cartesian-motion kernels'; +polyline: ... and the waypoint-list kernels';
-    #  +validity: ... and the sphere validity kernels')
-    return _stamp(flags + ["+paths", "+search"] + ([] if strict else ["+route"]) + ["+restart", "+startpath", "+globalpath", "+cartesian", "+polyline", "+validity"] + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
+    #  +validity: ... and the sphere validity kernels'; +pathvalid: ... and the path validity step's)
+    return _stamp(flags + ["+paths", "+search"] + ([] if strict else ["+route"]) + ["+restart", "+startpath", "+globalpath", "+cartesian", "+polyline", "+validity", "+pathvalid"] + ["only=" + os.environ.get("PIK_ONLY_D", "all")])
 
 
 def is_stale(lib: str = LIB) -> bool:

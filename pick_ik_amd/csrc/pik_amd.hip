@@ -27,6 +27,7 @@
 #include "pik_solver.hpp"
 #include "pik_startpath_ops.hpp"
 #include "pik_urdf.hpp"
+#include "pik_pathvalid_ops.hpp"
 #include "pik_validity_ops.hpp"
 
 namespace pik {
@@ -56,6 +57,7 @@ PIK_DECLARE_OPS_FAMILY(void, globalpath)
 PIK_DECLARE_OPS_FAMILY(void, cartesian)
 PIK_DECLARE_OPS_FAMILY(void, polyline)
 PIK_DECLARE_OPS_FAMILY(void, validity)
+PIK_DECLARE_OPS_FAMILY(void, pathvalid)
 } // namespace pik_exact
 namespace pik_common {
 char* error_buffer() { return ::pik::error_buffer(); }
@@ -91,7 +93,7 @@ enum Flavour {
 #endif
     N_FLAVOURS
 };
-enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, FAM_POLYLINE, FAM_VALIDITY, N_FAMILIES };
+enum Family { FAM_LAUNCH, FAM_PATH, FAM_SEARCH, FAM_ROUTE, FAM_RESTART, FAM_STARTPATH, FAM_GLOBALPATH, FAM_CARTESIAN, FAM_POLYLINE, FAM_VALIDITY, FAM_PATHVALID, N_FAMILIES };
 
 // What a handle keeps for pikamd_search_batch*: the option search_schedule and, per slot, the per-attempt rows of the
 // parallel schedule.  Every handle is allocated as one of these (create_solver); pikamd_solver itself is read by the
@@ -131,6 +133,10 @@ struct SolverExt : pikamd_solver {
     pik::ValidityModelK validity_model;
     pik::DevBuf validity_dev;
     uint32_t planar_xy_mask = 0;
+    // pikamd_set_path_validity: the switch, and per slot the `reached` of a path call whose caller keeps none (the
+    // validity step reads it)
+    int path_validity = 0;
+    pik::DevBuf pathvalid_rows[pik::N_SLOTS];
     SolverExt() {
         for (int& v : routed_passes) v = -1;
     }
@@ -157,14 +163,14 @@ const OpsLookup OPS_TABLE[N_FLAVOURS][N_FAMILIES] = {
      untyped<pik::GlobalPathOps, pik::globalpath_ops>, untyped<pik::CartesianOps, pik::cartesian_ops>,
      untyped<pik::PolylineOps, pik::polyline_ops>,
 #if defined(PIK_STRICT)
-     untyped<pik::ValidityOps, pik::validity_ops>},
+     untyped<pik::ValidityOps, pik::validity_ops>, untyped<pik::PathValidOps, pik::pathvalid_ops>},
 #else
-     nullptr}, // (the sphere validity test is the exact flavour's for every handle: validity_ops_of)
+     nullptr, nullptr}, // (the sphere validity test is the exact flavour's for every handle: validity_ops_of)
     {pik_exact::launch_ops, pik_exact::path_ops, pik_exact::search_ops, pik_exact::route_ops, pik_exact::restart_ops,
      pik_exact::startpath_ops, pik_exact::globalpath_ops, pik_exact::cartesian_ops, pik_exact::polyline_ops,
-     pik_exact::validity_ops},
-    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr, nullptr, nullptr},
-    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr, nullptr, nullptr},
+     pik_exact::validity_ops, pik_exact::pathvalid_ops},
+    {pik_common::launch_ops, nullptr, nullptr, pik_common::route_ops, pik_common::restart_ops, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {pik_common_goals::launch_ops, nullptr, nullptr, pik_common_goals::route_ops, pik_common_goals::restart_ops, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
 #endif
 };
 // ... and the namespace each flavour's kernels carry in profiles (what the *_kernel_name entry points report)
@@ -377,6 +383,31 @@ int validity_for_call(pikamd_solver* s, const char* who, const pik::ValidityOps*
     return *ops ? 0 : no_kernels(s->chain.dof);
 }
 
+// The validity step of a path call that starts from a joint state (pikamd_set_path_validity): the kernels of
+// pik_pathvalid.hpp in the flavour of the validity test, or null ops where the switch is off or the handle has no model.
+int path_validity_for_call(pikamd_solver* s, const char* who, const pik::PathValidOps** ops) {
+    *ops = nullptr;
+    if (!ext_of(s)->path_validity || !ext_of(s)->validity_set) return 0;
+    if (int rc = validity_chain_ok(s, who)) return rc;
+#if defined(PIK_STRICT)
+    *ops = ops_at<pik::PathValidOps>(FL_HOME, FAM_PATHVALID, s->chain.dof);
+#else
+    *ops = ops_at<pik::PathValidOps>(FL_EXACT, FAM_PATHVALID, s->chain.dof);
+#endif
+    return *ops ? 0 : no_kernels(s->chain.dof);
+}
+
+// `reached` of a path call for the validity step to read: the caller's array, or the slot's scratch, which grows only
+// past the largest earlier call on the slot
+int path_validity_reached(pikamd_solver* s, int slot, int64_t P, int32_t* callers, int32_t** out) {
+    *out = callers;
+    if (callers) return 0;
+    pik::DevBuf& buf = ext_of(s)->pathvalid_rows[slot];
+    if (int rc = buf.ensure(sizeof(int32_t) * (size_t)P)) return rc;
+    *out = (int32_t*)buf.p;
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -577,6 +608,7 @@ void pikamd_destroy(pikamd_solver* s) {
     for (auto& b : ext_of(s)->globalpath_rows) b.release();
     ext_of(s)->gate_params_dev.release();
     ext_of(s)->validity_dev.release();
+    for (auto& b : ext_of(s)->pathvalid_rows) b.release();
     for (auto& j : s->jobs) {
         j.dev.release();
         j.host.release();
@@ -1629,6 +1661,19 @@ pik::PathArgs path_args(int64_t P, int32_t W, const PathArrays& d) {
     return {P, W, 0, d.goal, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
 }
 
+// The walk of a call on `st` and, where the handle applies its validity model to paths (pikamd_set_path_validity), the
+// cut behind it.
+int run_paths(pikamd_solver* s, const pik::PathOps* ops, const pik::ParamsK& pk, const pik::PathArgs& a, hipStream_t st,
+              int slot) {
+    const pik::PathValidOps* vops = nullptr;
+    if (int rc = path_validity_for_call(s, SOLVE_PATHS.name, &vops)) return rc;
+    if (!vops) return ops->solve(s, pk, a, st, slot);
+    pik::PathArgs walk = a;
+    if (int rc = path_validity_reached(s, slot, a.P, a.reached, &walk.reached)) return rc;
+    if (int rc = ops->solve(s, pk, walk, st, slot)) return rc;
+    return vops->paths(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, a, walk.reached, st);
+}
+
 } // namespace
 
 extern "C" {
@@ -1646,7 +1691,7 @@ int32_t pikamd_solve_paths_device(pikamd_solver* s, const pikamd_params* p, int6
     const pik::PathOps* ops = path_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
     HIP_TRY(hipSetDevice(s->device));
-    return ops->solve(s, pk, path_args(P, W, d), (hipStream_t)stream, slot);
+    return run_paths(s, ops, pk, path_args(P, W, d), (hipStream_t)stream, slot);
 }
 
 int32_t pikamd_solve_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, const double* goal_pos_quat,
@@ -1672,7 +1717,7 @@ int32_t pikamd_solve_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, 
                             st.at<double>(sol),        st.at<int32_t>(status_),     st.at<double>(cost),
                             st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_)};
     if (int rc = st.upload()) return rc;
-    return st.finish(ops->solve(s, pk, path_args(P, W, dev), st.stream(), Staging::SLOT));
+    return st.finish(run_paths(s, ops, pk, path_args(P, W, dev), st.stream(), Staging::SLOT));
 }
 
 const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
@@ -2370,8 +2415,17 @@ int run_cartesian(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& 
     const pik::CartesianOps* fk_ops = ops_at<pik::CartesianOps>(flavour_of(s, nullptr, nullptr), FAM_CARTESIAN, dof);
     const pik::CartesianOps* walk_ops = ops_at<pik::CartesianOps>(flavour_of(s, p, nullptr), FAM_CARTESIAN, dof);
     if (!fk_ops || !walk_ops) return no_kernels(dof);
+    const pik::PathValidOps* vops = nullptr;
+    if (int rc = path_validity_for_call(s, CARTESIAN.name, &vops)) return rc;
     if (int rc = fk_ops->prepare(s, pk, a, st, slot)) return rc;
-    return walk_ops->walk(s, pk, a, st, slot);
+    if (!vops) return walk_ops->walk(s, pk, a, st, slot);
+    // with the validity step: the walk without the relative test (the prepare step above kept the caller's
+    // jump_factor: the minimum step count depends on it), then the cut and cartesian_tail with the caller's
+    pik::CartesianArgs walk = a;
+    walk.jump_factor = 0.0;
+    if (int rc = path_validity_reached(s, slot, a.path.P, a.path.reached, &walk.path.reached)) return rc;
+    if (int rc = walk_ops->walk(s, pk, walk, st, slot)) return rc;
+    return vops->cartesian(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, a, walk.path.reached, st);
 }
 
 } // namespace
@@ -2509,6 +2563,8 @@ int run_polyline(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& p
     const pik::PolylineOps* fk_ops = ops_at<pik::PolylineOps>(flavour_of(s, nullptr, nullptr), FAM_POLYLINE, dof);
     const pik::PolylineOps* walk_ops = ops_at<pik::PolylineOps>(flavour_of(s, p, nullptr), FAM_POLYLINE, dof);
     if (!fk_ops || !walk_ops) return no_kernels(dof);
+    const pik::PathValidOps* vops = nullptr;
+    if (int rc = path_validity_for_call(s, WAYPOINTS.name, &vops)) return rc;
     pik::PolylineArgs a = {};
     a.path = {P, W, 0, d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
     a.targets = d.targets;
@@ -2528,6 +2584,9 @@ int run_polyline(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& p
         a.seg = i;
         if (int rc = fk_ops->segment(s, pk, a, st, slot)) return rc;
         if (int rc = walk_ops->walk(s, pk, a, st, slot)) return rc;
+        // (pikamd_set_path_validity: the cut of this segment, in front of the next segment kernel)
+        if (vops)
+            if (int rc = vops->segment(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, a, st)) return rc;
     }
     return walk_ops->finish(s, pk, a, st, slot);
 }
@@ -2618,6 +2677,14 @@ int32_t pikamd_set_approximate_gate(pikamd_solver* s, const pikamd_gate* gate) {
     SolverExt* x = ext_of(s);
     x->gate_set = gate != nullptr;
     if (gate) x->gate = *gate;
+    return 0;
+}
+
+// ---- the validity model inside the path entry points that start from a joint state (pik_pathvalid.hpp) ----
+int32_t pikamd_set_path_validity(pikamd_solver* s, int32_t on) {
+    if (on != 0 && on != 1) return fail(PIKAMD_EINVAL, "pikamd_set_path_validity: on = %d: expected 0 or 1", (int)on);
+    if (int rc = check_solver(s)) return rc;
+    ext_of(s)->path_validity = on;
     return 0;
 }
 

@@ -806,6 +806,12 @@ class Solver {
         if (pikamd_set_validity_model(h_, nullptr) != 0) throw std::runtime_error(pikamd_last_error());
         n_spheres_ = 0;
     }
+    // pikamd_set_path_validity: on -- solve_paths, cartesian_paths and cartesian_waypoints end a path at the first
+    // waypoint whose answer the validity model refuses (PIKAMD_VALIDITY_REFUSED; the fraction counts the waypoints in
+    // front of it, the relative jump test runs over what is left); off (the default) -- they ignore the model
+    void set_path_validity(bool on) const {
+        if (pikamd_set_path_validity(h_, on ? 1 : 0) != 0) throw std::runtime_error(pikamd_last_error());
+    }
     // pikamd_validity_batch for one candidate: is `q` valid; *clearance (may be null): the smallest distance between
     // the surfaces of a pair; *centres (may be null): the sphere centres in the base frame, 3 numbers per sphere
     bool validity(const std::vector<double>& q, double* clearance = nullptr, std::vector<double>* centres = nullptr) const {

@@ -221,6 +221,7 @@ EXPORTED_SYMBOLS = (
     "pikamd_interpolate_poses", "pikamd_cartesian_paths", "pikamd_cartesian_paths_device", "pikamd_cartesian_kernel_name",
     "pikamd_cartesian_waypoints", "pikamd_cartesian_waypoints_device", "pikamd_cartesian_waypoints_kernel_name",
     "pikamd_set_validity_model", "pikamd_validity_batch", "pikamd_validity_batch_device",
+    "pikamd_set_path_validity",
 )
 
 _libs = {}
@@ -328,6 +329,8 @@ def lib(strict: bool = False):
     L.pikamd_set_approximate_gate.restype = C.c_int32
     L.pikamd_set_validity_model.argtypes = [vp, C.POINTER(ValidityModel)]
     L.pikamd_set_validity_model.restype = C.c_int32
+    L.pikamd_set_path_validity.argtypes = [vp, C.c_int32]
+    L.pikamd_set_path_validity.restype = C.c_int32
     L.pikamd_validity_batch.argtypes = [vp, C.c_int64, dp, ip, dp, dp]
     L.pikamd_validity_batch.restype = C.c_int32
     L.pikamd_validity_batch_device.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
@@ -649,6 +652,12 @@ class Solver:
         """no model (the default): every result is what it was"""
         self._chk(self._L.pikamd_set_validity_model(self._h, None))
         self._n_spheres = None
+
+    def set_path_validity(self, on: bool) -> None:
+        """pikamd_set_path_validity: on -- solve_paths, cartesian_paths and cartesian_waypoints (and their _device
+        forms) end a path at the first waypoint whose answer the handle's validity model refuses (VALIDITY_REFUSED);
+        off (the default) -- they ignore the model.  Without a model the switch changes nothing."""
+        self._chk(self._L.pikamd_set_path_validity(self._h, 1 if on else 0))
 
     def validity(self, q, centres: bool = False):
         """pikamd_validity_batch: (valid [n] bool, clearance [n]) of joint vectors q [n][dof]; centres=True: also the
