@@ -1558,6 +1558,8 @@ int check_call(const CallKind& c, const pikamd_solver* s, const pikamd_params* p
 class Staging {
   public:
     static constexpr int SLOT = pik::N_DEVICE_SLOTS + PIKAMD_MAX_HOST_JOBS - 1;
+    // the most regions a call registers: the arrays of the largest set (every stage_* function holds its set to this)
+    static constexpr int MAX_REGIONS = 13;
     Staging(pikamd_solver* s, const char* who) : s_(s), who_(who), J_(s->jobs[PIKAMD_MAX_HOST_JOBS - 1]) {}
     hipStream_t stream() const { return J_.stream; }
     // refuses while the job is in flight; the device, and the stream at its first use
@@ -1574,12 +1576,13 @@ class Staging {
     int out(void* dst, size_t bytes, bool always) { return add({nullptr, dst, total_, (dst || always) ? bytes : 0}, false); }
     // the buffers, once every region is registered
     int allocate() {
+        if (n_ > MAX_REGIONS) return fail(PIKAMD_EINVAL, "%s: %d arrays to stage: at most %d", who_, n_, MAX_REGIONS);
         if (int rc = J_.dev.ensure(total_)) return rc;
         return J_.host.ensure(total_);
     }
     template <class T>
     T* at(int region) const {
-        return r_[region].bytes ? reinterpret_cast<T*>((char*)J_.dev.p + r_[region].off) : nullptr;
+        return region < MAX_REGIONS && r_[region].bytes ? reinterpret_cast<T*>((char*)J_.dev.p + r_[region].off) : nullptr;
     }
     // the copy in
     int upload() {
@@ -1611,7 +1614,9 @@ class Staging {
         void* dst;
         size_t off, bytes;
     };
+    // (a region past the last place is counted and not kept: allocate() refuses the call)
     int add(const Region& r, bool input) {
+        if (n_ >= MAX_REGIONS) return n_++;
         r_[n_] = r;
         total_ += align8(r.bytes);
         if (input) in_bytes_ = total_;
@@ -1620,25 +1625,41 @@ class Staging {
     pikamd_solver* s_;
     const char* who_;
     pik::HostJob& J_;
-    Region r_[13]; // (pikamd_cartesian_waypoints registers 13)
+    Region r_[MAX_REGIONS];
     int n_ = 0;
     size_t in_bytes_ = 0, total_ = 0;
 };
 
 const char* tips_text(const pikamd_solver* s) { return s->n_tips > 1 ? "true" : "false"; }
 
-// the name of the kernel variant a path or search call runs: one lane, a team (exact flavours) or the cooperative descent
-const char* variant_name(const pikamd_solver* s, Flavour f, const char* stem, int lanes) {
+// the name of the kernel variant a path or search call runs: one lane, a team (exact flavours) or the cooperative
+// descent.  tips: the kernels have a template argument for several tip frames (the Cartesian motions' have none: they
+// are walked on one tip frame)
+const char* variant_name(const pikamd_solver* s, Flavour f, const char* stem, int lanes, bool tips = true) {
     pikamd_solver* m = const_cast<pikamd_solver*>(s);
+    char tail[8] = "";
+    if (tips) snprintf(tail, sizeof tail, ",%s", tips_text(s));
     const char* ns = FLAVOUR_NAMESPACE[f];
     const int dof = s->chain.dof;
     if (lanes == 1)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_kernel<%d,%s>", ns, stem, dof, tips_text(s));
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_kernel<%d%s>", ns, stem, dof, tail);
     else if (is_exact(f))
         snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_team_kernel<%d,%d>", ns, stem, dof, lanes);
     else
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_wide_kernel<%d,%d,%s>", ns, stem, dof, lanes, tips_text(s));
+        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_%s_wide_kernel<%d,%d%s>", ns, stem, dof, lanes, tail);
     return m->kernel_name;
+}
+// ... of a path call of P paths in the flavour a path call runs in ("" where the name functions have nothing to name)
+const char* path_variant_name(const pikamd_solver* s, const pikamd_params* p, int64_t P, const char* stem, bool tips = true) {
+    if (!s || !p) return "";
+    const Flavour f = flavour_of(s, p, nullptr);
+    return variant_name(s, f, stem, pik::path_lanes(s, P, is_exact(f)), tips);
+}
+
+// what every stream-ordered entry point refuses of its slot
+int check_slot(int32_t slot) {
+    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    return 0;
 }
 
 } // namespace
@@ -1659,6 +1680,27 @@ struct PathArrays {
 
 pik::PathArgs path_args(int64_t P, int32_t W, const PathArrays& d) {
     return {P, W, 0, d.goal, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
+}
+
+// the arrays a set of them holds (one pointer each): what its stage_* function registers
+template <class Arrays>
+constexpr int n_arrays() {
+    return (int)(sizeof(Arrays) / sizeof(void*));
+}
+
+// registers the arrays of a synchronous path call of P paths and W waypoints, allocates, and gives the device's
+int stage_paths(Staging& st, const pikamd_solver* s, const PathArrays& h, int64_t P, int32_t W, PathArrays& dev) {
+    static_assert(n_arrays<PathArrays>() <= Staging::MAX_REGIONS, "Staging::MAX_REGIONS");
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
+    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), start = st.in(h.start, sizeof(double) * d * paths);
+    const int step = st.in(h.max_step, sizeof(double) * d);
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, true);
+    const int stats = st.out(h.stats, sizeof(pikamd_stats) * rows, true), status = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached = st.out(h.reached, sizeof(int32_t) * paths, true);
+    if (int rc = st.allocate()) return rc;
+    dev = {st.at<const double>(goal), st.at<const double>(start), st.at<const double>(step), st.at<double>(sol),
+           st.at<int32_t>(status),    st.at<double>(cost),        st.at<pikamd_stats>(stats), st.at<int32_t>(reached)};
+    return 0;
 }
 
 // The walk of a call on `st` and, where the handle applies its validity model to paths (pikamd_set_path_validity), the
@@ -1685,7 +1727,7 @@ int32_t pikamd_solve_paths_device(pikamd_solver* s, const pikamd_params* p, int6
     const PathArrays d = {d_goal_pos_quat, d_start, d_max_joint_step, d_solution, d_status, d_final_cost, d_stats, d_reached};
     pik::ParamsK pk;
     if (int rc = check_call(SOLVE_PATHS, s, p, P, W, d.required_null(), pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_slot(slot)) return rc;
     if (P == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::PathOps* ops = path_ops_of(s, p);
@@ -1706,24 +1748,14 @@ int32_t pikamd_solve_paths(pikamd_solver* s, const pikamd_params* p, int64_t P, 
     if (!ops) return no_kernels(s->chain.dof);
     Staging st(s, SOLVE_PATHS.name);
     if (int rc = st.begin()) return rc;
-    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
-    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), start_ = st.in(h.start, sizeof(double) * d * paths);
-    const int step = st.in(h.max_step, sizeof(double) * d);
-    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, true);
-    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, true), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
-    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, true);
-    if (int rc = st.allocate()) return rc;
-    const PathArrays dev = {st.at<const double>(goal), st.at<const double>(start_), st.at<const double>(step),
-                            st.at<double>(sol),        st.at<int32_t>(status_),     st.at<double>(cost),
-                            st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_)};
+    PathArrays dev;
+    if (int rc = stage_paths(st, s, h, P, W, dev)) return rc;
     if (int rc = st.upload()) return rc;
     return st.finish(run_paths(s, ops, pk, path_args(P, W, dev), st.stream(), Staging::SLOT));
 }
 
 const char* pikamd_path_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
-    if (!s || !p) return "";
-    const Flavour f = flavour_of(s, p, nullptr);
-    return variant_name(s, f, "path", pik::path_lanes(s, P, is_exact(f)));
+    return path_variant_name(s, p, P, "path");
 }
 
 } // extern "C"
@@ -1743,12 +1775,31 @@ struct StartPathArrays {
     bool required_null() const { return !goal || !seed || !solution || !status; }
 };
 
-// what both entry points refuse: check_call's list for a path call, then the attempts
-int check_search_paths(const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, int32_t K,
+// what the entry points of both kinds (SEARCH_PATHS, SEARCH_GLOBAL_PATHS) refuse: check_call's list for a path call of
+// the kind, then the attempts
+int check_search_paths(const CallKind& kind, const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, int32_t K,
                        const StartPathArrays& d, pik::ParamsK& pk) {
-    if (int rc = check_call(SEARCH_PATHS, s, p, P, W, d.required_null(), pk)) return rc;
+    if (int rc = check_call(kind, s, p, P, W, d.required_null(), pk)) return rc;
     if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
-        return fail(PIKAMD_EINVAL, "%s: max_attempts %d: expected 1..%d", SEARCH_PATHS.name, (int)K, PIKAMD_MAX_ATTEMPTS);
+        return fail(PIKAMD_EINVAL, "%s: max_attempts %d: expected 1..%d", kind.name, (int)K, PIKAMD_MAX_ATTEMPTS);
+    return 0;
+}
+
+// registers the arrays of a synchronous call of P paths and W waypoints, allocates, and gives the device's
+int stage_startpath(Staging& st, const pikamd_solver* s, const StartPathArrays& h, int64_t P, int32_t W, StartPathArrays& dev) {
+    static_assert(n_arrays<StartPathArrays>() <= Staging::MAX_REGIONS, "Staging::MAX_REGIONS");
+    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
+    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), seed = st.in(h.seed, sizeof(double) * d * paths);
+    const int guess = st.in(h.guess, sizeof(double) * d * paths), step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached = st.out(h.reached, sizeof(int32_t) * paths, false), attempts = st.out(h.attempts, sizeof(int32_t) * paths, false);
+    const int totals = st.out(h.totals, sizeof(pikamd_stats) * paths, false);
+    if (int rc = st.allocate()) return rc;
+    dev = {st.at<const double>(goal), st.at<const double>(seed), st.at<const double>(guess),  st.at<const double>(step),
+           st.at<double>(sol),        st.at<int32_t>(status),    st.at<double>(cost),         st.at<pikamd_stats>(stats),
+           st.at<int32_t>(reached),   st.at<int32_t>(attempts),  st.at<pikamd_stats>(totals)};
     return 0;
 }
 
@@ -1798,8 +1849,8 @@ int32_t pikamd_search_paths_device(pikamd_solver* s, const pikamd_params* p, int
     const StartPathArrays d = {d_goal_pos_quat, d_seed,  d_initial_guess, d_max_joint_step, d_solution, d_status,
                                d_final_cost,    d_stats, d_reached,       d_attempts,       d_totals};
     pik::ParamsK pk;
-    if (int rc = check_search_paths(s, p, P, W, max_attempts, d, pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_search_paths(SEARCH_PATHS, s, p, P, W, max_attempts, d, pk)) return rc;
+    if (int rc = check_slot(slot)) return rc;
     if (P == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::StartPathOps* ops = startpath_ops_of(s, p);
@@ -1818,26 +1869,15 @@ int32_t pikamd_search_paths(pikamd_solver* s, const pikamd_params* p, int64_t P,
     const StartPathArrays h = {goal_pos_quat, seed,  initial_guess, max_joint_step, solution, status,
                                final_cost,    stats, reached,       attempts,       totals};
     pik::ParamsK pk;
-    if (int rc = check_search_paths(s, p, P, W, max_attempts, h, pk)) return rc;
+    if (int rc = check_search_paths(SEARCH_PATHS, s, p, P, W, max_attempts, h, pk)) return rc;
     if (P == 0) return 0;
     if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
     const pik::StartPathOps* ops = startpath_ops_of(s, p);
     if (!ops) return no_kernels(s->chain.dof);
     Staging st(s, SEARCH_PATHS.name);
     if (int rc = st.begin()) return rc;
-    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
-    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), seed_ = st.in(h.seed, sizeof(double) * d * paths);
-    const int guess = st.in(h.guess, sizeof(double) * d * paths), step = st.in(h.max_step, sizeof(double) * d);
-    // (the outputs a caller left out are not written by the kernels either: no bytes)
-    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
-    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
-    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), attempts_ = st.out(h.attempts, sizeof(int32_t) * paths, false);
-    const int totals_ = st.out(h.totals, sizeof(pikamd_stats) * paths, false);
-    if (int rc = st.allocate()) return rc;
-    const StartPathArrays dev = {st.at<const double>(goal), st.at<const double>(seed_), st.at<const double>(guess),
-                                 st.at<const double>(step), st.at<double>(sol),         st.at<int32_t>(status_),
-                                 st.at<double>(cost),       st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_),
-                                 st.at<int32_t>(attempts_), st.at<pikamd_stats>(totals_)};
+    StartPathArrays dev;
+    if (int rc = stage_startpath(st, s, h, P, W, dev)) return rc;
     pik::StartPathArgs a;
     if (int rc = startpath_args(s, Staging::SLOT, P, W, max_attempts, dev, rng_seed, problem_offset, a)) return rc;
     if (int rc = st.upload()) return rc;
@@ -1845,9 +1885,7 @@ int32_t pikamd_search_paths(pikamd_solver* s, const pikamd_params* p, int64_t P,
 }
 
 const char* pikamd_search_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
-    if (!s || !p) return "";
-    const Flavour f = flavour_of(s, p, nullptr);
-    return variant_name(s, f, "startpath", pik::path_lanes(s, P, is_exact(f)));
+    return path_variant_name(s, p, P, "startpath");
 }
 
 } // extern "C"
@@ -1870,6 +1908,7 @@ struct SearchArrays {
 
 // registers the arrays of a synchronous search call of B problems and K attempts, allocates, and gives the device's
 int stage_search(Staging& st, const pikamd_solver* s, const SearchArrays& h, int64_t B, int32_t K, SearchArrays& dev) {
+    static_assert(n_arrays<SearchArrays>() <= Staging::MAX_REGIONS, "Staging::MAX_REGIONS");
     const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, n = (size_t)B, rows = n * (size_t)K;
     const int goal = st.in(h.goal, sizeof(double) * g7 * n), seed = st.in(h.seed, sizeof(double) * d * n);
     const int guess = st.in(h.guess, sizeof(double) * d * n);
@@ -1986,7 +2025,7 @@ int32_t pikamd_search_batch_device(pikamd_solver* s, const pikamd_params* p, int
                             d_final_cost,    d_stats, d_attempts,      d_all_solution, d_all_status};
     pik::ParamsK pk;
     if (int rc = check_call(SEARCH, s, p, B, max_attempts, d.required_null(), pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_slot(slot)) return rc;
     if (B == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::SearchOps* ops = search_ops_of(s, p);
@@ -2037,9 +2076,77 @@ const char* pikamd_search_kernel_name(const pikamd_solver* s, const pikamd_param
 
 namespace {
 
-// The attempts of one call on `stream` (device pointers in `r`: B, K, user_guess, the key, the primary outputs and
-// all_*; goal / seed apart).  sync_between: the host-pointer entry point -- the open count is read back behind every
-// fold, and no attempt is enqueued once it is zero.
+// The record of the memetic solves of a global-mode call of B problems: every attempt writes its rows, read by the
+// step behind it.
+pik::BatchRecord restart_record(int64_t B, const double* goal, const double* seed, const double* guess,
+                                int64_t problem_offset, double* solution, int* status, double* cost, void* stats) {
+    pik::BatchRecord rec;
+    std::memset(&rec, 0, sizeof rec);
+    rec.B = B;
+    rec.goal = goal;
+    rec.seed = seed;
+    rec.guess = guess;
+    rec.problem_offset = problem_offset;
+    rec.solution = solution;
+    rec.status = status;
+    rec.cost = cost;
+    rec.stats = stats;
+    return rec;
+}
+
+// the open count of the slot's restart list, in its counter block
+unsigned* restart_open_count(const pikamd_solver* s, int slot) {
+    return (unsigned*)(s->counters + pik::COUNTER_BLOCK * (size_t)slot + 128);
+}
+
+// THE restart loop of a global-mode call on `stream`: up to K attempts of the memetic solver on `rec` -- attempt 0 by
+// run_solve on every problem, an attempt behind it by the restart launcher on the open problems of `list` -- and behind
+// every attempt the caller's step, behind(attempt, last), which folds the attempt's rows and writes the next list and
+// its count (n_list).  The call is keyed by rng_seed (restart_attempt_seed); `who` names it in a PIKAMD_EHIP text.
+// sync_between: the host-pointer entry point -- the open count is read back behind every step but the last, and no
+// attempt is enqueued once it is zero; the stream-ordered entry point never synchronises here.  Every failure in here
+// marks the slot's counters dirty (a launch that failed half-way leaves counters behind: the next call on the slot
+// clears them, in here -- behind the caller's prepare kernel, which reads and writes no counter); what a caller does in
+// front -- scratch, reserve, prepare, its lookups -- does not.
+template <class Behind>
+int run_restart_attempts(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pik::RestartOps* ops,
+                         pik::BatchRecord rec, const int* list, const unsigned* n_list, int K, uint64_t rng_seed,
+                         const char* who, hipStream_t stream, int slot, bool sync_between, Behind behind) {
+    auto give_up = [&](int rc) {
+        s->counters_dirty[slot] = true;
+        return rc;
+    };
+    if (s->counters_dirty[slot]) {
+        HIP_TRY(hipMemsetAsync(s->counters + pik::COUNTER_BLOCK * (size_t)slot, 0, pik::COUNTER_BLOCK, stream));
+        s->counters_dirty[slot] = false;
+    }
+    long long open = rec.B;
+    for (int a = 0; a < K; ++a) {
+        const bool last = a == K - 1;
+        const unsigned long long seed_a = pik::restart_attempt_seed(rng_seed, a);
+        if (a == 0) {
+            if (int rc = run_solve(s, p, pk, &rec, 1, seed_a, stream, slot)) return give_up(rc);
+        } else {
+            pik::BatchRecord copy = rec; // (the launch fills in `start`)
+            if (int rc = ops->attempt(s, p, pk, &copy, seed_a, list, sync_between ? open : -1, stream, slot))
+                return give_up(rc);
+        }
+        if (int rc = behind(a, last)) return give_up(rc);
+        if (sync_between && !last) {
+            unsigned cnt = 0;
+            hipError_t e = hipMemcpyAsync(&cnt, n_list, sizeof cnt, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return give_up(fail(PIKAMD_EHIP, "%s: %s", who, hipGetErrorString(e)));
+            open = (long long)cnt;
+            if (open == 0) break;
+        }
+    }
+    return 0;
+}
+
+// One pikamd_search_global_batch call on `stream` (device pointers in `r`: B, K, user_guess, the key, the primary
+// outputs and all_*; goal / seed apart): the rows and lists in the slot's scratch, and behind an attempt the gate, the
+// validity rows and the fold.
 int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pik::RestartOps* ops,
                       pik::RestartArgs r, const double* d_goal, const double* d_seed, hipStream_t stream, int slot,
                       bool sync_between) {
@@ -2053,7 +2160,6 @@ int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::Param
     if (int rc = buf.ensure(total)) return rc;
     if (int rc = ops->reserve(s, p, pk, r.B, slot)) return rc;
     char* w = (char*)buf.p;
-    unsigned* n_list = (unsigned*)(s->counters + pik::COUNTER_BLOCK * (size_t)slot + 128);
     r.guess = (double*)(w + off_guess);
     r.row_solution = (double*)(w + off_sol);
     r.row_cost = (const double*)(w + off_cost);
@@ -2061,64 +2167,28 @@ int run_search_global(pikamd_solver* s, const pikamd_params* p, const pik::Param
     r.row_status = (int*)(w + off_status);
     r.open = (int*)(w + off_open);
     r.list = (int*)(w + off_list);
-    r.n_list = n_list;
+    r.n_list = restart_open_count(s, slot);
     r.every = (r.all_solution || r.all_status) ? 1 : 0;
     r.goal = d_goal;
     r.seed = d_seed;
     if (int rc = gate_for_call(s, pk, slot, stream, &r.gate, &r.gate_joint, &r.gate_params)) return rc;
     // the validity step behind the gate: the rows kernel of the sphere model, where the handle has one
     const pik::ValidityOps* vops = nullptr;
-    if (int rc = validity_for_call(s, "pikamd_search_global_batch", &vops)) return rc;
-    pik::ValidityRows vr = {r.B, r.every, 0, r.open, r.row_solution, r.row_status, d_seed};
-    pik::BatchRecord rec;
-    std::memset(&rec, 0, sizeof rec);
-    rec.B = r.B;
-    rec.goal = d_goal;
-    rec.seed = d_seed;
-    rec.guess = r.guess;
-    rec.problem_offset = r.problem_offset;
-    rec.solution = (double*)(w + off_sol);
-    rec.status = (int*)(w + off_status);
-    rec.cost = (double*)(w + off_cost);
-    rec.stats = w + off_stats;
-    // (a launch that failed half-way leaves counters behind: the next call on the slot clears them)
-    auto give_up = [&](int rc) {
-        s->counters_dirty[slot] = true;
-        return rc;
-    };
-    if (s->counters_dirty[slot]) {
-        HIP_TRY(hipMemsetAsync(s->counters + pik::COUNTER_BLOCK * (size_t)slot, 0, pik::COUNTER_BLOCK, stream));
-        s->counters_dirty[slot] = false;
-    }
+    if (int rc = validity_for_call(s, SEARCH_GLOBAL.name, &vops)) return rc;
+    const pik::ValidityRows vr = {r.B, r.every, 0, r.open, r.row_solution, r.row_status, d_seed};
     if (int rc = ops->prepare(s, pk, r, stream, slot)) return rc;
-    long long open = r.B;
-    for (int a = 0; a < r.K; ++a) {
-        const unsigned long long seed_a = pik::restart_attempt_seed(r.rng_seed, a);
-        if (a == 0) {
-            if (int rc = run_solve(s, p, pk, &rec, 1, seed_a, stream, slot)) return give_up(rc);
-        } else {
-            pik::BatchRecord copy = rec; // (the launch fills in `start`)
-            if (int rc = ops->attempt(s, p, pk, &copy, seed_a, r.list, sync_between ? open : -1, stream, slot))
-                return give_up(rc);
-        }
-        r.attempt = a;
-        r.last = (a == r.K - 1) ? 1 : 0;
+    const pik::BatchRecord rec = restart_record(r.B, d_goal, d_seed, r.guess, r.problem_offset, r.row_solution, r.row_status,
+                                                (double*)(w + off_cost), w + off_stats);
+    return run_restart_attempts(s, p, pk, ops, rec, r.list, r.n_list, r.K, r.rng_seed, SEARCH_GLOBAL.name, stream, slot,
+                                sync_between, [&](int attempt, bool last) {
+        r.attempt = attempt;
+        r.last = last ? 1 : 0;
         if (r.gate)
-            if (int rc = ops->gate(s, pk, r, stream, slot)) return give_up(rc);
+            if (int rc = ops->gate(s, pk, r, stream, slot)) return rc;
         if (vops)
-            if (int rc = vops->rows(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, vr, stream))
-                return give_up(rc);
-        if (int rc = ops->fold(s, pk, r, stream, slot)) return give_up(rc);
-        if (sync_between && !r.last) {
-            unsigned cnt = 0;
-            hipError_t e = hipMemcpyAsync(&cnt, n_list, sizeof cnt, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return give_up(fail(PIKAMD_EHIP, "pikamd_search_global_batch: %s", hipGetErrorString(e)));
-            open = (long long)cnt;
-            if (open == 0) break;
-        }
-    }
-    return 0;
+            if (int rc = vops->rows(ext_of(s)->validity_dev.p, ext_of(s)->validity_model.n_spheres, vr, stream)) return rc;
+        return ops->fold(s, pk, r, stream, slot);
+    });
 }
 
 } // namespace
@@ -2135,7 +2205,7 @@ int32_t pikamd_search_global_batch_device(pikamd_solver* s, const pikamd_params*
                             d_final_cost,    d_stats, d_attempts,      d_all_solution, d_all_status};
     pik::ParamsK pk;
     if (int rc = check_call(SEARCH_GLOBAL, s, p, B, max_attempts, d.required_null(), pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_slot(slot)) return rc;
     if (B == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::RestartOps* ops = restart_ops_of(s, p, pk);
@@ -2171,19 +2241,8 @@ int32_t pikamd_search_global_batch(pikamd_solver* s, const pikamd_params* p, int
 // ---- Cartesian paths from a pose, memetic start (pik_globalpath.hpp) ---------------------------------
 namespace {
 
-// what both entry points refuse: check_call's list for a path call in global mode, then the attempts
-int check_search_global_paths(const pikamd_solver* s, const pikamd_params* p, int64_t P, int32_t W, int32_t K,
-                              const StartPathArrays& d, pik::ParamsK& pk) {
-    if (int rc = check_call(SEARCH_GLOBAL_PATHS, s, p, P, W, d.required_null(), pk)) return rc;
-    if (K < 1 || K > PIKAMD_MAX_ATTEMPTS)
-        return fail(PIKAMD_EINVAL, "%s: max_attempts %d: expected 1..%d", SEARCH_GLOBAL_PATHS.name, (int)K, PIKAMD_MAX_ATTEMPTS);
-    return 0;
-}
-
-// The attempts of one call on `stream` (device pointers in `d`): per attempt the memetic solve of waypoint 0 for the
-// open paths -- run_solve for attempt 0, the restart launcher behind it, as run_search_global -- and the tail kernel.
-// sync_between: the host-pointer entry point -- the open count is read back behind every tail, and no attempt is
-// enqueued once it is zero.
+// One call on `stream` (device pointers in `d`): the rows and lists in the slot's scratch, and the restart loop
+// (run_restart_attempts) over the memetic solves of waypoint 0 with the tail kernel behind every attempt.
 int run_search_global_paths(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& pk, const pik::RestartOps* rops,
                             const pik::GlobalPathOps* gops, int64_t P, int32_t W, int32_t K, const StartPathArrays& d,
                             uint64_t rng_seed, int64_t problem_offset, hipStream_t stream, int slot, bool sync_between) {
@@ -2194,7 +2253,6 @@ int run_search_global_paths(pikamd_solver* s, const pikamd_params* p, const pik:
     if (int rc = buf.ensure(l.total)) return rc;
     if (int rc = rops->reserve(s, p, pk, P, slot)) return rc;
     char* w = (char*)buf.p;
-    unsigned* n_list = (unsigned*)(s->counters + pik::COUNTER_BLOCK * (size_t)slot + 128);
     pik::GlobalPathArgs a = {};
     a.P = P;
     a.W = W;
@@ -2228,51 +2286,16 @@ int run_search_global_paths(pikamd_solver* s, const pikamd_params* p, const pik:
     a.best = (int*)(w + l.off_best);
     a.open = (int*)(w + l.off_open);
     a.list = (int*)(w + l.off_list);
-    a.n_list = n_list;
-    pik::BatchRecord rec;
-    std::memset(&rec, 0, sizeof rec);
-    rec.B = P;
-    rec.goal = a.goal0;
-    rec.seed = d.seed;
-    rec.guess = a.guess;
-    rec.problem_offset = problem_offset;
-    rec.solution = (double*)(w + l.off_m_solution);
-    rec.status = (int*)(w + l.off_m_status);
-    rec.cost = (double*)(w + l.off_m_cost);
-    rec.stats = w + l.off_m_stats;
-    // (a launch that failed half-way leaves counters behind: the next call on the slot clears them)
-    auto give_up = [&](int rc) {
-        s->counters_dirty[slot] = true;
-        return rc;
-    };
-    if (s->counters_dirty[slot]) {
-        HIP_TRY(hipMemsetAsync(s->counters + pik::COUNTER_BLOCK * (size_t)slot, 0, pik::COUNTER_BLOCK, stream));
-        s->counters_dirty[slot] = false;
-    }
+    a.n_list = restart_open_count(s, slot);
     if (int rc = gops->prepare(s, pk, a, stream, slot)) return rc;
-    long long open = P;
-    for (int at = 0; at < K; ++at) {
-        const unsigned long long seed_a = pik::restart_attempt_seed(rng_seed, at);
-        if (at == 0) {
-            if (int rc = run_solve(s, p, pk, &rec, 1, seed_a, stream, slot)) return give_up(rc);
-        } else {
-            pik::BatchRecord copy = rec; // (the launch fills in `start`)
-            if (int rc = rops->attempt(s, p, pk, &copy, seed_a, a.list, sync_between ? open : -1, stream, slot))
-                return give_up(rc);
-        }
-        a.attempt = at;
-        a.last = (at == K - 1) ? 1 : 0;
-        if (int rc = gops->tail(s, pk, a, stream, slot)) return give_up(rc);
-        if (sync_between && !a.last) {
-            unsigned cnt = 0;
-            hipError_t e = hipMemcpyAsync(&cnt, n_list, sizeof cnt, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return give_up(fail(PIKAMD_EHIP, "%s: %s", SEARCH_GLOBAL_PATHS.name, hipGetErrorString(e)));
-            open = (long long)cnt;
-            if (open == 0) break;
-        }
-    }
-    return 0;
+    const pik::BatchRecord rec = restart_record(P, a.goal0, d.seed, a.guess, problem_offset, (double*)(w + l.off_m_solution),
+                                                (int*)(w + l.off_m_status), (double*)(w + l.off_m_cost), w + l.off_m_stats);
+    return run_restart_attempts(s, p, pk, rops, rec, a.list, a.n_list, K, rng_seed, SEARCH_GLOBAL_PATHS.name, stream, slot,
+                                sync_between, [&](int attempt, bool last) {
+        a.attempt = attempt;
+        a.last = last ? 1 : 0;
+        return gops->tail(s, pk, a, stream, slot);
+    });
 }
 
 } // namespace
@@ -2289,8 +2312,8 @@ int32_t pikamd_search_global_paths_device(pikamd_solver* s, const pikamd_params*
     const StartPathArrays d = {d_goal_pos_quat, d_seed,  d_initial_guess, d_max_joint_step, d_solution, d_status,
                                d_final_cost,    d_stats, d_reached,       d_attempts,       d_totals};
     pik::ParamsK pk;
-    if (int rc = check_search_global_paths(s, p, P, W, max_attempts, d, pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_search_paths(SEARCH_GLOBAL_PATHS, s, p, P, W, max_attempts, d, pk)) return rc;
+    if (int rc = check_slot(slot)) return rc;
     if (P == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     const pik::RestartOps* rops = restart_ops_of(s, p, pk);
@@ -2309,7 +2332,7 @@ int32_t pikamd_search_global_paths(pikamd_solver* s, const pikamd_params* p, int
     const StartPathArrays h = {goal_pos_quat, seed,  initial_guess, max_joint_step, solution, status,
                                final_cost,    stats, reached,       attempts,       totals};
     pik::ParamsK pk;
-    if (int rc = check_search_global_paths(s, p, P, W, max_attempts, h, pk)) return rc;
+    if (int rc = check_search_paths(SEARCH_GLOBAL_PATHS, s, p, P, W, max_attempts, h, pk)) return rc;
     if (P == 0) return 0;
     // (both kernel sets: the GLOBAL-mode one of waypoint 0 and the local-mode one of the waypoints behind it)
     if (int rc = maybe_self_test(s, p)) return rc;
@@ -2321,28 +2344,15 @@ int32_t pikamd_search_global_paths(pikamd_solver* s, const pikamd_params* p, int
     if (!rops || !gops) return no_kernels(s->chain.dof);
     Staging st(s, SEARCH_GLOBAL_PATHS.name);
     if (int rc = st.begin()) return rc;
-    const size_t d = (size_t)s->chain.dof, g7 = 7 * (size_t)s->n_tips, paths = (size_t)P, rows = paths * (size_t)W;
-    const int goal = st.in(h.goal, sizeof(double) * g7 * rows), seed_ = st.in(h.seed, sizeof(double) * d * paths);
-    const int guess = st.in(h.guess, sizeof(double) * d * paths), step = st.in(h.max_step, sizeof(double) * d);
-    // (the outputs a caller left out are not written by the kernels either: no bytes)
-    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
-    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
-    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), attempts_ = st.out(h.attempts, sizeof(int32_t) * paths, false);
-    const int totals_ = st.out(h.totals, sizeof(pikamd_stats) * paths, false);
-    if (int rc = st.allocate()) return rc;
-    const StartPathArrays dev = {st.at<const double>(goal), st.at<const double>(seed_), st.at<const double>(guess),
-                                 st.at<const double>(step), st.at<double>(sol),         st.at<int32_t>(status_),
-                                 st.at<double>(cost),       st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_),
-                                 st.at<int32_t>(attempts_), st.at<pikamd_stats>(totals_)};
+    StartPathArrays dev;
+    if (int rc = stage_startpath(st, s, h, P, W, dev)) return rc;
     if (int rc = st.upload()) return rc;
     return st.finish(run_search_global_paths(s, p, pk, rops, gops, P, W, max_attempts, dev, rng_seed, problem_offset,
                                              st.stream(), Staging::SLOT, true));
 }
 
 const char* pikamd_search_global_paths_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
-    if (!s || !p) return "";
-    const Flavour f = flavour_of(s, p, nullptr);
-    return variant_name(s, f, "globalpath", pik::path_lanes(s, P, is_exact(f)));
+    return path_variant_name(s, p, P, "globalpath");
 }
 
 } // extern "C"
@@ -2379,22 +2389,49 @@ struct CartesianArrays {
     double *fraction, *goals;
 };
 
-// what both entry points refuse: check_call's list for a path call, the parameter object, several tip frames
+// what the entry points of both Cartesian kinds (CARTESIAN, WAYPOINTS) refuse first: check_call's list for a path call
+// of the kind (its arrays apart), the parameter object, several tip frames
+int check_cartesian_call(const CallKind& kind, const pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c,
+                         int64_t P, int32_t W, pik::ParamsK& pk) {
+    if (int rc = check_call(kind, s, p, P, W, false, pk)) return rc;
+    if (int rc = check_cartesian(kind.name, c)) return rc;
+    if (s->n_tips > 1)
+        return fail(PIKAMD_EUNSUPPORTED, "%s: %d tip frames: a Cartesian motion is that of one tip frame", kind.name, s->n_tips);
+    return 0;
+}
+
+// what both entry points refuse: check_cartesian_call's list, then the arrays
 int check_cartesian_paths(const pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P, int32_t W,
                           const CartesianArrays& d, pik::ParamsK& pk) {
-    if (int rc = check_call(CARTESIAN, s, p, P, W, false, pk)) return rc;
-    if (int rc = check_cartesian(CARTESIAN.name, c)) return rc;
-    if (s->n_tips > 1)
-        return fail(PIKAMD_EUNSUPPORTED, "%s: %d tip frames: a Cartesian motion is that of one tip frame", CARTESIAN.name, s->n_tips);
+    if (int rc = check_cartesian_call(CARTESIAN, s, p, c, P, W, pk)) return rc;
     if (!d.steps) return fail(PIKAMD_EINVAL, "%s: steps must not be NULL (a path with steps[p] > W was not walked)", CARTESIAN.name);
     if (P > 0 && (!d.start || !d.target || !d.solution || !d.status))
         return fail(PIKAMD_EINVAL, "%s: start, target, solution and status must not be NULL", CARTESIAN.name);
     return 0;
 }
 
+// registers the arrays of a synchronous call of P paths and W rows, allocates, and gives the device's
+int stage_cartesian(Staging& st, const pikamd_solver* s, const CartesianArrays& h, int64_t P, int32_t W, CartesianArrays& dev) {
+    static_assert(n_arrays<CartesianArrays>() <= Staging::MAX_REGIONS, "Staging::MAX_REGIONS");
+    const size_t d = (size_t)s->chain.dof, paths = (size_t)P, rows = paths * (size_t)W;
+    const int start = st.in(h.start, sizeof(double) * d * paths), target = st.in(h.target, sizeof(double) * 7 * paths);
+    const int step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes -- the poses apart, which the
+    // walk reads)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached = st.out(h.reached, sizeof(int32_t) * paths, false), steps = st.out(h.steps, sizeof(int32_t) * paths, true);
+    const int fraction = st.out(h.fraction, sizeof(double) * paths, false), goals = st.out(h.goals, sizeof(double) * 7 * rows, true);
+    if (int rc = st.allocate()) return rc;
+    dev = {st.at<const double>(start), st.at<const double>(target), st.at<const double>(step),  st.at<double>(sol),
+           st.at<int32_t>(status),     st.at<double>(cost),         st.at<pikamd_stats>(stats), st.at<int32_t>(reached),
+           st.at<int32_t>(steps),      st.at<double>(fraction),     st.at<double>(goals)};
+    return 0;
+}
+
 pik::CartesianArgs cartesian_args(const pikamd_cartesian* c, int64_t P, int32_t W, const CartesianArrays& d) {
     pik::CartesianArgs a = {};
-    a.path = {P, W, 0, d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
+    a.path = path_args(P, W, {d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached});
     a.target = d.target;
     a.goals = d.goals;
     a.steps = d.steps;
@@ -2461,7 +2498,7 @@ int32_t pikamd_cartesian_paths_device(pikamd_solver* s, const pikamd_params* p, 
                          d_stats, d_reached, d_steps,         d_fraction, d_goals};
     pik::ParamsK pk;
     if (int rc = check_cartesian_paths(s, p, c, P, W, d, pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_slot(slot)) return rc;
     if (P == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     HIP_TRY(hipSetDevice(s->device));
@@ -2486,35 +2523,14 @@ int32_t pikamd_cartesian_paths(pikamd_solver* s, const pikamd_params* p, const p
     if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
     Staging st(s, CARTESIAN.name);
     if (int rc = st.begin()) return rc;
-    const size_t d = (size_t)s->chain.dof, paths = (size_t)P, rows = paths * (size_t)W;
-    const int start_ = st.in(h.start, sizeof(double) * d * paths), target_ = st.in(h.target, sizeof(double) * 7 * paths);
-    const int step = st.in(h.max_step, sizeof(double) * d);
-    // (the outputs a caller left out are not written by the kernels either: no bytes -- the poses apart, which the
-    // walk reads)
-    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
-    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
-    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), steps_ = st.out(h.steps, sizeof(int32_t) * paths, true);
-    const int fraction_ = st.out(h.fraction, sizeof(double) * paths, false), goals_ = st.out(h.goals, sizeof(double) * 7 * rows, true);
-    if (int rc = st.allocate()) return rc;
-    const CartesianArrays dev = {st.at<const double>(start_), st.at<const double>(target_), st.at<const double>(step),
-                                 st.at<double>(sol),          st.at<int32_t>(status_),      st.at<double>(cost),
-                                 st.at<pikamd_stats>(stats_), st.at<int32_t>(reached_),     st.at<int32_t>(steps_),
-                                 st.at<double>(fraction_),    st.at<double>(goals_)};
+    CartesianArrays dev;
+    if (int rc = stage_cartesian(st, s, h, P, W, dev)) return rc;
     if (int rc = st.upload()) return rc;
     return st.finish(run_cartesian(s, p, pk, cartesian_args(c, P, W, dev), st.stream(), Staging::SLOT));
 }
 
 const char* pikamd_cartesian_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
-    if (!s || !p) return "";
-    const Flavour f = flavour_of(s, p, nullptr);
-    pikamd_solver* m = const_cast<pikamd_solver*>(s);
-    const int lanes = pik::path_lanes(s, P, is_exact(f)), dof = s->chain.dof;
-    if (lanes == 1)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_cartesian_kernel<%d>", FLAVOUR_NAMESPACE[f], dof);
-    else
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_cartesian_%s_kernel<%d,%d>", FLAVOUR_NAMESPACE[f],
-                 is_exact(f) ? "team" : "wide", dof, lanes);
-    return m->kernel_name;
+    return path_variant_name(s, p, P, "cartesian", false);
 }
 
 } // extern "C"
@@ -2538,19 +2554,38 @@ struct WaypointArrays {
     double *fraction, *goals;
 };
 
-// what both entry points refuse: pikamd_cartesian_paths' list, then the target list's own
+// what both entry points refuse: check_cartesian_call's list, then the target list's own and the arrays
 int check_cartesian_waypoints(const pikamd_solver* s, const pikamd_params* p, const pikamd_cartesian* c, int64_t P, int32_t S,
                               int32_t W, const WaypointArrays& d, pik::ParamsK& pk) {
     const char* const who = WAYPOINTS.name;
-    if (int rc = check_call(WAYPOINTS, s, p, P, W, false, pk)) return rc;
-    if (int rc = check_cartesian(who, c)) return rc;
-    if (s->n_tips > 1)
-        return fail(PIKAMD_EUNSUPPORTED, "%s: %d tip frames: a Cartesian motion is that of one tip frame", who, s->n_tips);
+    if (int rc = check_cartesian_call(WAYPOINTS, s, p, c, P, W, pk)) return rc;
     if (!d.steps) return fail(PIKAMD_EINVAL, "%s: steps must not be NULL (a path with steps[p] > W has a segment that did not fit)", who);
     if (S < 1) return fail(PIKAMD_EINVAL, "%s: %d targets per path: expected S >= 1", who, (int)S);
     if (S > W) return fail(PIKAMD_EINVAL, "%s: %d targets in %d rows: expected S <= W (every segment needs a row)", who, (int)S, (int)W);
     if (P > 0 && (!d.start || !d.targets || !d.solution || !d.status))
         return fail(PIKAMD_EINVAL, "%s: start, targets, solution and status must not be NULL", who);
+    return 0;
+}
+
+// registers the arrays of a synchronous call of P paths, S targets and W rows, allocates, and gives the device's
+int stage_waypoints(Staging& st, const pikamd_solver* s, const WaypointArrays& h, int64_t P, int32_t S, int32_t W,
+                    WaypointArrays& dev) {
+    static_assert(n_arrays<WaypointArrays>() <= Staging::MAX_REGIONS, "Staging::MAX_REGIONS");
+    const size_t d = (size_t)s->chain.dof, paths = (size_t)P, rows = paths * (size_t)W, segs = paths * (size_t)S;
+    const int start = st.in(h.start, sizeof(double) * d * paths), targets = st.in(h.targets, sizeof(double) * 7 * segs);
+    const int count = st.in(h.n_targets, sizeof(int32_t) * paths), step = st.in(h.max_step, sizeof(double) * d);
+    // (the outputs a caller left out are not written by the kernels either: no bytes -- the poses apart, which the
+    // walk reads)
+    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
+    const int stats = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status = st.out(h.status, sizeof(int32_t) * rows, true);
+    const int reached = st.out(h.reached, sizeof(int32_t) * paths, false), steps = st.out(h.steps, sizeof(int32_t) * paths, true);
+    const int segsteps = st.out(h.segment_steps, sizeof(int32_t) * segs, false);
+    const int fraction = st.out(h.fraction, sizeof(double) * paths, false), goals = st.out(h.goals, sizeof(double) * 7 * rows, true);
+    if (int rc = st.allocate()) return rc;
+    dev = {st.at<const double>(start), st.at<const double>(targets), st.at<const int32_t>(count), st.at<const double>(step),
+           st.at<double>(sol),         st.at<int32_t>(status),       st.at<double>(cost),         st.at<pikamd_stats>(stats),
+           st.at<int32_t>(reached),    st.at<int32_t>(steps),        st.at<int32_t>(segsteps),    st.at<double>(fraction),
+           st.at<double>(goals)};
     return 0;
 }
 
@@ -2566,7 +2601,7 @@ int run_polyline(pikamd_solver* s, const pikamd_params* p, const pik::ParamsK& p
     const pik::PathValidOps* vops = nullptr;
     if (int rc = path_validity_for_call(s, WAYPOINTS.name, &vops)) return rc;
     pik::PolylineArgs a = {};
-    a.path = {P, W, 0, d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached};
+    a.path = path_args(P, W, {d.goals, d.start, d.max_step, d.solution, d.status, d.cost, d.stats, d.reached});
     a.targets = d.targets;
     a.n_targets = d.n_targets;
     a.goals = d.goals;
@@ -2605,7 +2640,7 @@ int32_t pikamd_cartesian_waypoints_device(pikamd_solver* s, const pikamd_params*
                         d_stats,  d_reached, d_steps,     d_segment_steps,  d_fraction,  d_goals};
     pik::ParamsK pk;
     if (int rc = check_cartesian_waypoints(s, p, c, P, S, W, d, pk)) return rc;
-    if (slot < 0 || slot >= PIKAMD_MAX_SLOTS) return fail(PIKAMD_EINVAL, "slot out of range");
+    if (int rc = check_slot(slot)) return rc;
     if (P == 0) return 0;
     // (no automatic self test here: stream-ordered, see pikamd_solve_batches_device)
     HIP_TRY(hipSetDevice(s->device));
@@ -2631,39 +2666,17 @@ int32_t pikamd_cartesian_waypoints(pikamd_solver* s, const pikamd_params* p, con
     if (int rc = maybe_self_test(s, p)) return rc; // (the local-mode kernel set, as pikamd_solve_batch)
     Staging st(s, WAYPOINTS.name);
     if (int rc = st.begin()) return rc;
-    const size_t d = (size_t)s->chain.dof, paths = (size_t)P, rows = paths * (size_t)W, segs = paths * (size_t)S;
-    const int start_ = st.in(h.start, sizeof(double) * d * paths), targets_ = st.in(h.targets, sizeof(double) * 7 * segs);
-    const int count = st.in(h.n_targets, sizeof(int32_t) * paths), step = st.in(h.max_step, sizeof(double) * d);
-    // (the outputs a caller left out are not written by the kernels either: no bytes -- the poses apart, which the
-    // walk reads)
-    const int sol = st.out(h.solution, sizeof(double) * d * rows, true), cost = st.out(h.cost, sizeof(double) * rows, false);
-    const int stats_ = st.out(h.stats, sizeof(pikamd_stats) * rows, false), status_ = st.out(h.status, sizeof(int32_t) * rows, true);
-    const int reached_ = st.out(h.reached, sizeof(int32_t) * paths, false), steps_ = st.out(h.steps, sizeof(int32_t) * paths, true);
-    const int segsteps = st.out(h.segment_steps, sizeof(int32_t) * segs, false);
-    const int fraction_ = st.out(h.fraction, sizeof(double) * paths, false), goals_ = st.out(h.goals, sizeof(double) * 7 * rows, true);
-    if (int rc = st.allocate()) return rc;
+    WaypointArrays dev;
+    if (int rc = stage_waypoints(st, s, h, P, S, W, dev)) return rc;
+    // (the per-path state: a buffer of its own, in the slot's scratch)
     pik::DevBuf& state = ext_of(s)->polyline_rows[Staging::SLOT];
     if (int rc = state.ensure(pik::polyline_state_bytes(P))) return rc;
-    const WaypointArrays dev = {st.at<const double>(start_), st.at<const double>(targets_), st.at<const int32_t>(count),
-                                st.at<const double>(step),   st.at<double>(sol),            st.at<int32_t>(status_),
-                                st.at<double>(cost),         st.at<pikamd_stats>(stats_),   st.at<int32_t>(reached_),
-                                st.at<int32_t>(steps_),      st.at<int32_t>(segsteps),      st.at<double>(fraction_),
-                                st.at<double>(goals_)};
     if (int rc = st.upload()) return rc;
     return st.finish(run_polyline(s, p, pk, c, P, S, W, dev, state.p, st.stream(), Staging::SLOT));
 }
 
 const char* pikamd_cartesian_waypoints_kernel_name(const pikamd_solver* s, const pikamd_params* p, int64_t P) {
-    if (!s || !p) return "";
-    const Flavour f = flavour_of(s, p, nullptr);
-    pikamd_solver* m = const_cast<pikamd_solver*>(s);
-    const int lanes = pik::path_lanes(s, P, is_exact(f)), dof = s->chain.dof;
-    if (lanes == 1)
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_polyline_kernel<%d>", FLAVOUR_NAMESPACE[f], dof);
-    else
-        snprintf(m->kernel_name, sizeof m->kernel_name, "%s::ik_polyline_%s_kernel<%d,%d>", FLAVOUR_NAMESPACE[f],
-                 is_exact(f) ? "team" : "wide", dof, lanes);
-    return m->kernel_name;
+    return path_variant_name(s, p, P, "polyline", false);
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
-"""Raw ctypes calls of the six path / search entry points of include/pick_ik_amd.h -- every argument as the C ABI takes
+"""Raw ctypes calls of the path / search entry points of include/pick_ik_amd.h -- every argument as the C ABI takes
 it, any of them NULL -- for the tests of what they refuse, what they report and which optional arrays they need
-(tests/test_gpu_abi_characterisation.py, test_gpu_path.py, test_gpu_search.py, test_gpu_search_global.py)."""
+(tests/test_gpu_abi_characterisation.py, test_gpu_path.py, test_gpu_search.py, test_gpu_search_global.py,
+test_gpu_startpath.py, test_gpu_globalpath.py, test_gpu_cartesian.py, test_gpu_polyline.py)."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +13,13 @@ DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 PATH_ARRAYS = ("goal", "start", "max_joint_step", "solution", "status", "final_cost", "stats", "reached")
 SEARCH_ARRAYS = ("goal", "seed", "initial_guess", "solution", "status", "final_cost", "stats", "attempts",
                  "all_solution", "all_status")
-PATH_OUTPUTS, SEARCH_OUTPUTS = PATH_ARRAYS[3:], SEARCH_ARRAYS[3:]
+STARTPATH_ARRAYS = ("goal", "seed", "initial_guess", "max_joint_step", "solution", "status", "final_cost", "stats",
+                    "reached", "attempts", "totals")
+CARTESIAN_ARRAYS = ("start", "target", "max_joint_step", "solution", "status", "final_cost", "stats", "reached", "steps",
+                    "fraction", "goals")
+WAYPOINT_ARRAYS = ("start", "targets", "n_targets", "max_joint_step", "solution", "status", "final_cost", "stats",
+                   "reached", "steps", "segment_steps", "fraction", "goals")
+PATH_OUTPUTS, SEARCH_OUTPUTS, STARTPATH_OUTPUTS = PATH_ARRAYS[3:], SEARCH_ARRAYS[3:], STARTPATH_ARRAYS[4:]
 _CTYPE = {np.dtype(np.float64): DP, np.dtype(np.int32): IP}
 
 
@@ -43,6 +50,26 @@ def search(L, h, p, B, K, a, device=False, slot=0, global_mode=False, rng_seed=0
     return fn(*args, None, slot) if device else fn(*args)
 
 
+def search_paths(L, h, p, P, W, K, a, rng_seed=0, problem_offset=0, device=False, slot=0, global_mode=False):
+    """pikamd_search[_global]_paths[_device]; a: name -> array of STARTPATH_ARRAYS (absent or None: NULL)"""
+    x = [_ptr(a.get(k)) for k in STARTPATH_ARRAYS]
+    fn = getattr(L, "pikamd_search" + ("_global" if global_mode else "") + "_paths" + ("_device" if device else ""))
+    args = [h, _params(p), P, W, *x[:4], C.c_uint64(rng_seed), problem_offset, K, *x[4:]]
+    return fn(*args, None, slot) if device else fn(*args)
+
+
+def cartesian_paths(L, h, p, c, P, W, a, device=False, slot=0):
+    """pikamd_cartesian_paths[_device]; c: the pikamd_cartesian (None: NULL); a: name -> array of CARTESIAN_ARRAYS"""
+    args = [h, _params(p), _params(c), P, W, *[_ptr(a.get(k)) for k in CARTESIAN_ARRAYS]]
+    return L.pikamd_cartesian_paths_device(*args, None, slot) if device else L.pikamd_cartesian_paths(*args)
+
+
+def cartesian_waypoints(L, h, p, c, P, S, W, a, device=False, slot=0):
+    """pikamd_cartesian_waypoints[_device]; c: the pikamd_cartesian (None: NULL); a: name -> array of WAYPOINT_ARRAYS"""
+    args = [h, _params(p), _params(c), P, S, W, *[_ptr(a.get(k)) for k in WAYPOINT_ARRAYS]]
+    return L.pikamd_cartesian_waypoints_device(*args, None, slot) if device else L.pikamd_cartesian_waypoints(*args)
+
+
 def last_error(L):
     return L.pikamd_last_error().decode()
 
@@ -66,6 +93,27 @@ def search_arrays(s, goals, seed, initial_guess, K):
                 status=np.full(B, -77, dtype=np.int32), final_cost=np.full(B, -7.5),
                 stats=_stats_pattern((B,)), attempts=np.full(B, -77, dtype=np.int32),
                 all_solution=np.full((B, K, s.dof), -7.5), all_status=np.full((B, K), -77, dtype=np.int32))
+
+
+def startpath_arrays(s, goals, seed, guess, step):
+    """every array of a pikamd_search[_global]_paths call, the outputs filled with a pattern no call returns"""
+    P, W = goals.shape[:2]
+    return dict(goal=goals, seed=seed, initial_guess=guess, max_joint_step=step, solution=np.full((P, W, s.dof), -7.5),
+                status=np.full((P, W), -77, dtype=np.int32), final_cost=np.full((P, W), -7.5),
+                stats=_stats_pattern((P, W)), reached=np.full(P, -77, dtype=np.int32),
+                attempts=np.full(P, -77, dtype=np.int32), totals=_stats_pattern((P,)))
+
+
+def cartesian_outputs(P, W, dof):
+    """every output of a pikamd_cartesian_paths call, filled with a pattern no call returns"""
+    return dict(solution=np.full((P, W, dof), -7.5), status=np.full((P, W), -77, dtype=np.int32),
+                final_cost=np.full((P, W), -7.5), stats=_stats_pattern((P, W)), reached=np.full(P, -77, dtype=np.int32),
+                steps=np.full(P, -77, dtype=np.int32), fraction=np.full(P, -7.5), goals=np.full((P, W, 7), -7.5))
+
+
+def waypoint_outputs(P, S, W, dof):
+    """... and of a pikamd_cartesian_waypoints call"""
+    return dict(cartesian_outputs(P, W, dof), segment_steps=np.full((P, S), -77, dtype=np.int32))
 
 
 def check_optional_arrays(call, fresh, optional, outputs):

@@ -16,6 +16,7 @@ import pytest
 import pick_ik_amd as pk
 from pick_ik_amd import robots
 from pick_ik_amd.solver import STATS_DTYPE
+from tests import abi_calls as A
 from tests import cartesian_reference as CR
 
 pytestmark = pytest.mark.gpu
@@ -210,14 +211,9 @@ ORDER = ("solution", "status", "final_cost", "stats", "reached", "steps", "fract
 
 
 def _raw(s, p, c, start, target, step, a, P=None, w=W):
-    ptr = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
-    cast = lambda x, t: None if x is None else x.ctypes.data_as(t)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    return s._L.pikamd_cartesian_paths(
-        s._h, None if p is None else C.byref(p), None if c is None else C.byref(c), len(start) if P is None else P, w,
-        cast(start, dp), cast(target, dp), cast(step, dp), cast(a["solution"], dp), cast(a["status"], ip),
-        cast(a["final_cost"], dp), ptr(a["stats"]), cast(a["reached"], ip), cast(a["steps"], ip), cast(a["fraction"], dp),
-        cast(a["goals"], dp))
+    """pikamd_cartesian_paths as the C ABI takes it (tests/abi_calls.py); a: the outputs"""
+    return A.cartesian_paths(s._L, s._h, p, c, len(start) if P is None else P, w,
+                             dict(a, start=start, target=target, max_joint_step=step))
 
 
 def test_every_optional_array_may_be_absent(O):

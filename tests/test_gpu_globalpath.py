@@ -6,7 +6,6 @@ include/pick_ik_amd.h (tests/globalpath_reference.py holds that loop), so everyt
 against the loop over the CPU oracle for the exact builds, against the loop over the handle's own calls for every
 flavour, every variant of the tail kernel against the one-lane variant.  tests/test_globalpath_cpu.py shows that the
 fixtures reach every class of the loop."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -26,10 +25,7 @@ from tests.test_gpu_path import FLOATING_BASE, mimic_panda
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-#: the array arguments of the C signature in its order
-ARRAYS = ("goal", "seed", "initial_guess", "max_joint_step", "solution", "status", "final_cost", "stats", "reached",
-          "attempts", "totals")
-OUTPUTS = ARRAYS[4:]
+OUTPUTS = A.STARTPATH_OUTPUTS
 
 
 @pytest.fixture(scope="module")
@@ -55,20 +51,12 @@ def own_loop(s, ch, p, pl, goals, seed, K, step=None, **kw):
     return GP.reference_search_global_paths(one, local, ch, goals, seed, K, step, **kw)
 
 
-def raw_call(L, h, p, P, W, K, a, rng_seed=0, problem_offset=0, device=False, slot=0):
-    """pikamd_search_global_paths[_device]; a: name -> array of ARRAYS (absent or None: NULL)"""
-    x = [A._ptr(a.get(k)) for k in ARRAYS]
-    args = [h, None if p is None else C.byref(p), P, W, *x[:4], C.c_uint64(rng_seed), problem_offset, K, *x[4:]]
-    return L.pikamd_search_global_paths_device(*args, None, slot) if device else L.pikamd_search_global_paths(*args)
+def raw_call(*args, **kw):
+    """pikamd_search_global_paths[_device] as the C ABI takes it (tests/abi_calls.py)"""
+    return A.search_paths(*args, global_mode=True, **kw)
 
 
-def fresh_arrays(s, goals, seed, guess, step):
-    """every array of a call, the outputs filled with a pattern no call returns"""
-    P, W = goals.shape[:2]
-    return dict(goal=goals, seed=seed, initial_guess=guess, max_joint_step=step, solution=np.full((P, W, s.dof), -7.5),
-                status=np.full((P, W), -77, dtype=np.int32), final_cost=np.full((P, W), -7.5),
-                stats=A._stats_pattern((P, W)), reached=np.full(P, -77, dtype=np.int32),
-                attempts=np.full(P, -77, dtype=np.int32), totals=A._stats_pattern((P,)))
+fresh_arrays = A.startpath_arrays
 
 
 _oracle_runs = {}

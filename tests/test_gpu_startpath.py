@@ -5,7 +5,6 @@ Its result is DEFINED by the loop of local-mode solve_batch and solve_paths call
 (tests/startpath_reference.py holds that loop), so everything here compares at tolerance zero: against the loop over
 the CPU oracle for the exact builds, against the loop over the handle's own calls for the fast flavour, every kernel
 variant against every other.  tests/test_startpath_cpu.py shows that the fixtures reach every class of the loop."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -23,10 +22,7 @@ from tests.test_gpu_fuzz import random_chain
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-#: the array arguments of the C signature in its order
-ARRAYS = ("goal", "seed", "initial_guess", "max_joint_step", "solution", "status", "final_cost", "stats", "reached",
-          "attempts", "totals")
-OUTPUTS = ARRAYS[4:]
+OUTPUTS = A.STARTPATH_OUTPUTS
 
 
 @pytest.fixture(scope="module")
@@ -45,20 +41,9 @@ def own_solve(s, p):
     return lambda g, sd, ig: s.solve_batch(p, g, sd, initial_guess=ig)
 
 
-def raw_call(L, h, p, P, W, K, a, rng_seed=0, problem_offset=0, device=False, slot=0):
-    """pikamd_search_paths[_device]; a: name -> array of ARRAYS (absent or None: NULL)"""
-    x = [A._ptr(a.get(k)) for k in ARRAYS]
-    args = [h, None if p is None else C.byref(p), P, W, *x[:4], C.c_uint64(rng_seed), problem_offset, K, *x[4:]]
-    return L.pikamd_search_paths_device(*args, None, slot) if device else L.pikamd_search_paths(*args)
-
-
-def fresh_arrays(s, goals, seed, guess, step):
-    """every array of a call, the outputs filled with a pattern no call returns"""
-    P, W = goals.shape[:2]
-    return dict(goal=goals, seed=seed, initial_guess=guess, max_joint_step=step, solution=np.full((P, W, s.dof), -7.5),
-                status=np.full((P, W), -77, dtype=np.int32), final_cost=np.full((P, W), -7.5),
-                stats=A._stats_pattern((P, W)), reached=np.full(P, -77, dtype=np.int32),
-                attempts=np.full(P, -77, dtype=np.int32), totals=A._stats_pattern((P,)))
+#: pikamd_search_paths[_device] as the C ABI takes it, and every array of a call (tests/abi_calls.py)
+raw_call = A.search_paths
+fresh_arrays = A.startpath_arrays
 
 
 @pytest.mark.parametrize("case", list(SP.CASES))
